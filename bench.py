@@ -12,14 +12,20 @@ the flat gradient arena issued in slices beside the backward (Lightning-DDP sema
 src/models/smp/train.py:122-133); per-GPU batch stays 16, so scaling is "weak" (`--scaling strong`
 keeps the global batch at 16 instead: 16/N frames per GPU).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) including
+Prints ONE JSON line on rank 0: metric, value (frames/s), unit, higher_is_better, dtype, ms_per_step (one timed step) and the
+workload's configuration.  A plain run sets up, warms up, times `--steps` steps and prints that line; `--dump-outputs DIR` also
+writes what the last timed step computed as DIR/<name>.npy (see dump_outputs).  The last timed step starts from the seeded
+weights, BatchNorm statistics and optimizer state, so its loss and outputs are the same in every run with the same arguments.  `--full` adds the measurements that take time
+of their own, after the timed steps:
+  power         -- socket power and shader clock of the GPU, sampled during the timed steps (PowerSampler)
   roofline      -- the MFMA conv kernels (conv_mfma_kernel + gemm1x1_kernel + wgrad_mfma_kernel), timed live with HIP
                    events on the launch stream: algorithmic conv FLOPs (6 * MACs * frames, SURVEY.md
                    section 8d) / summed kernel time, vs 2.5 PFLOP/s dense bf16.  `achieved` comes from an
                    untimed extra pass with every launch on one stream (kernels alone); the brackets of the
-                   timed, stream-overlapped steps are reported beside it under `overlapped`
+                   timed, stream-overlapped steps are reported beside it under `overlapped` (`--profile-timed`)
+  roofline_hbm  -- the BatchNorm sweeps of the same untimed pass against the HBM roof
   cpu_baseline  -- the torch-CPU oracle (a port, not the reference's own files) on the same workload at 704x704,
-                   2 frames per step, 1 warm-up + 3 timed steps, median; fp32 (`value`) and bf16 autocast
+                   2 frames per step, 1 warm-up + 3 timed steps, median; fp32 (`value`) and bf16 autocast (`--no-cpu-baseline` skips it)
 """
 import argparse
 import json
@@ -196,6 +202,32 @@ def cpu_baseline(arch, enc, classes, size, batch=2, timed=3):
                       f'time budget): fp32 {[round(t, 2) for t in t32]} s, bf16 autocast {[round(t, 2) for t in t16]} s'}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, arrays):
+    """--dump-outputs: write each output of the last timed step as <outdir>/<name>.npy -- integer tensors (counts) as float64, the rest
+    as float32.  `arrays` maps name -> (tensor, cap): an output of more than `cap` elements is written as a fixed sample of its
+    flattened elements (indices drawn with numpy seed 0, sorted, duplicates dropped), so two builds given the same arguments write
+    the same positions.  The caps keep the files under DUMP_LIMIT_BYTES in all.  The last timed training step starts from the seeded
+    state (see main), so two runs of one build write the same values up to the rounding of the float-atomic reductions."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    total = 0
+    for name, (t, cap) in arrays.items():
+        t = t.detach()
+        if t.numel() > cap:
+            idx = np.unique(np.random.default_rng(0).integers(0, t.numel(), size=cap))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        dt = torch.float64 if (t.dtype == torch.float64 or not t.is_floating_point()) else torch.float32
+        a = t.to(dtype=dt).cpu().numpy()
+        total += a.nbytes
+        if total > DUMP_LIMIT_BYTES:
+            raise RuntimeError(f'--dump-outputs: {name} takes the outputs past {DUMP_LIMIT_BYTES >> 20} MB')
+        np.save(os.path.join(outdir, f'{name}.npy'), a)
+    print(f'[bench] wrote {len(arrays)} output(s), {total / 2**20:.1f} MB, to {outdir}', file=sys.stderr, flush=True)
+
+
 _RESULT_OUT = sys.stdout
 
 ENSEMBLE = (('LM', 'unetplusplus', 'resnet101', ['Lumen']), ('FC_LC', 'linknet', 'resnet50', ['Lipid core', 'Fibrous cap']),
@@ -235,6 +267,7 @@ def bench_ensemble(args):
     def step():
         # replayed graphs of the three nets are started together, each on its plan's own stream, and joined in order (SegNet.forward_async)
         handles = [net.forward_async(x, normalize=False) if (side_by_side and net.use_graph) else None for net, _ in nets]
+        logits = []
         for (net, classes), h in zip(nets, handles):
             if os.environ.get('OCTSEG_BENCH_TRACE'):
                 print(f'[bench] {net.arch}/{net.encoder_name}', file=sys.stderr, flush=True)
@@ -243,6 +276,8 @@ def bench_ensemble(args):
                 ch = MODELS_META[cl]['index'] if z.shape[1] > 1 else 0
                 L.check(lib.octseg_mask_assemble(L.ptr(z), B, z.shape[1], S, S, int(ch), L.ptr(stack), OUT, OUT, 4, CLASS_IDS[cl] - 1,
                                                  L.ptr(rows), L.ptr(rows), L.stream_ptr()))
+            logits.append(z)
+        return logits
 
     print(f'[bench] ensemble of 3 nets, {B} frame(s) per step, {args.dtype}, {"hipGraph replay" if not args.no_graph else "eager"}: warm-up',
           file=sys.stderr, flush=True)
@@ -251,25 +286,13 @@ def bench_ensemble(args):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        logits = step()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    # roofline pass: eager, one stream, every conv launch bracketed by HIP events
-    for net, _ in nets:
-        net.use_graph = False
-    prof = (C.c_double * 12)()
-    L.check(lib.octseg_debug_set_serial(1))
-    step(); torch.cuda.synchronize()
-    L.check(lib.octseg_profile_start())
-    n_alone = 3
-    for _ in range(n_alone):
-        step()
-    torch.cuda.synchronize()
-    L.check(lib.octseg_profile_stop(prof))
-    L.check(lib.octseg_debug_set_serial(0))
+    if args.dump_outputs:    # the 4-class masks and each net's logits; the 32 + 3 x 8 MB caps bind from 3 frames per step on
+        dump_outputs(args.dump_outputs, {'masks': (stack, 8 << 20),
+                                         **{f'logits_{name}': (z, 2 << 20) for (name, *_), z in zip(ENSEMBLE, logits)}})
     macs = sum(net.fwd_macs(B, S, S) for net, _ in nets) / B
-    ach = prof[1] / (prof[0] * 1e-3) / 1e12 if prof[0] > 0 else 0.0
-    peak = 157.3 if args.dtype == 'fp32' else 2500.0
     out = {'metric': f'OCT frames/sec (704x704, {args.dtype}) 3-net ensemble inference', 'value': round(B * args.steps / dt, 3), 'unit': 'frames/s',
            'n_gpus': 1, 'steps': args.steps, 'warmup': max(args.warmup, 3), 'ms_per_step': round(dt / args.steps * 1e3, 3),
            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': args.dtype,
@@ -277,13 +300,30 @@ def bench_ensemble(args):
            'config': {'multi_gpu': 'replicas only: frames are independent, this workload runs on one GPU', 'fc_lc_forwards_per_batch': 1,   # the reference runs the FC_LC net once per class = twice (predict.py:70-76)
                       'workload': f'ensemble LM unetplusplus/resnet101 + FC_LC linknet/resnet50 (2 classes) + VV unet/resnet50, 704x704 -> 4-class '
                                   f'1000x1000 masks, batch {B}, eval forward + GPU mask assembly, {"hipGraph replay" if not args.no_graph else "eager launches"}',
-                      'global_batch': B, 'parallelism': 'dp1', 'gmac_fwd_per_frame': round(macs / 1e9, 2)},
-           'roofline': {'bound': 'mfma', 'kernel': 'conv_mfma_kernel + gemm1x1_kernel (forward, BatchNorm folded)', 'achieved': round(ach, 2),
-                        'peak': peak, 'unit': 'TFLOP/s', 'frac': round(ach / peak, 4), 'traffic': None,
-                        'launches_per_step': round(prof[2] / n_alone, 1), 'kernel_ms_per_step': round(prof[0] / n_alone, 3),
-                        'avg_launch_ms': round(prof[0] / max(prof[2], 1.0), 4), 'algorithmic_gflop_per_frame': round(2 * macs / 1e9, 1),
-                        'note': 'HIP-event brackets of every conv launch in an untimed eager one-stream pass of the same step'}}
-    print(f'[bench] ensemble: {out["value"]} frames/s, {out["ms_per_step"]} ms/step; conv kernels alone {ach:.1f} TFLOP/s', file=sys.stderr, flush=True)
+                      'global_batch': B, 'parallelism': 'dp1', 'gmac_fwd_per_frame': round(macs / 1e9, 2)}}
+    print(f'[bench] ensemble: {out["value"]} frames/s, {out["ms_per_step"]} ms/step', file=sys.stderr, flush=True)
+    if args.full:
+        # roofline pass: eager, one stream, every conv launch bracketed by HIP events
+        for net, _ in nets:
+            net.use_graph = False
+        prof = (C.c_double * 12)()
+        L.check(lib.octseg_debug_set_serial(1))
+        step(); torch.cuda.synchronize()
+        L.check(lib.octseg_profile_start())
+        n_alone = 3
+        for _ in range(n_alone):
+            step()
+        torch.cuda.synchronize()
+        L.check(lib.octseg_profile_stop(prof))
+        L.check(lib.octseg_debug_set_serial(0))
+        ach = prof[1] / (prof[0] * 1e-3) / 1e12 if prof[0] > 0 else 0.0
+        peak = 157.3 if args.dtype == 'fp32' else 2500.0
+        out['roofline'] = {'bound': 'mfma', 'kernel': 'conv_mfma_kernel + gemm1x1_kernel (forward, BatchNorm folded)', 'achieved': round(ach, 2),
+                           'peak': peak, 'unit': 'TFLOP/s', 'frac': round(ach / peak, 4), 'traffic': None,
+                           'launches_per_step': round(prof[2] / n_alone, 1), 'kernel_ms_per_step': round(prof[0] / n_alone, 3),
+                           'avg_launch_ms': round(prof[0] / max(prof[2], 1.0), 4), 'algorithmic_gflop_per_frame': round(2 * macs / 1e9, 1),
+                           'note': 'HIP-event brackets of every conv launch in an untimed eager one-stream pass of the same step'}
+        print(f'[bench] ensemble: conv kernels alone {ach:.1f} TFLOP/s', file=sys.stderr, flush=True)
     print(json.dumps(out), file=_RESULT_OUT, flush=True)
 
 
@@ -310,15 +350,22 @@ def main():
     ap.add_argument('--loss', default='dice', choices=['dice', 'bce', 'dice+bce'], help="criterion (the reference's is Dice, model.py:55)")
     ap.add_argument('--dtype', default=None, choices=['bf16', 'fp32', 'fp16'], help='default: bf16 (training workloads), fp16 (ensemble)')
     ap.add_argument('--optimizer', default='Adam')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also measure power, the roofline passes and the CPU baseline (see the module docstring)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB in all)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: leave the CPU baseline out')
     ap.add_argument('--backend', default='nccl', help='torch.distributed backend (nccl = RCCL; gloo only to rehearse the N > 1 path on one GPU)')
-    ap.add_argument('--profile-timed', action='store_true', help='also bracket every launch of the timed steps with HIP events (roofline.overlapped)')
+    ap.add_argument('--profile-timed', action='store_true',
+                    help='--full: also bracket every launch of the timed steps with HIP events (roofline.overlapped)')
     ap.add_argument('--train-graph', action='store_true',
                     help='forward + Dice + backward of a step as one replayed hipGraph (octseg_net_train_step); N = 1 or without the exchange')
     ap.add_argument('--force-exchange', action='store_true',
                     help='N = 1: run the data-parallel step anyway -- a one-rank RCCL group, buffer broadcast and the sliced all-reduce '
                          'beside the backward (exercises the nccl branch on a single GPU; the collectives are identities)')
     args = ap.parse_args()
+    if args.profile_timed and not args.full:
+        ap.error('--profile-timed reports under the roofline of --full: give both')
     if args.workload == 'ensemble_704_fp16':
         args.dtype = args.dtype or 'fp16'
         if not torch.cuda.is_available():
@@ -387,6 +434,20 @@ def main():
     opt = model.configure_optimizers()
     img, mask = make_batch(B, classes, S, seed=1234 + rank)
     img, mask = img.to(dev), mask.to(dev)
+    # The last timed step starts again from the seeded state: weights, BatchNorm statistics and Adam's moments as they are now.  The
+    # weight gradients sum split-K partials with float atomics, so a step's gradients vary in their last bits from run to run; Adam's
+    # update (about lr * sign(g) for the first steps) turns that into lr-sized weight differences that the following steps grow.
+    # Restarting the last step makes what it computes -- the reported loss and the --dump-outputs arrays -- a function of the seeded
+    # inputs alone, the same in every run up to rounding.  One in-place copy per run, enqueued like the steps.
+    state = [t for t in (net.arena.data, net.bn_buffers, net.num_batches_tracked, opt.m, opt.v) if t is not None]
+    seeded = [t.clone() for t in state]
+    seeded_count = opt.step_count
+
+    def restore_seeded_state():
+        for t, s in zip(state, seeded):
+            t.copy_(s)
+        opt.step_count = seeded_count
+        net.params_changed()
 
     def step():
         if dp and not no_bcast:
@@ -398,7 +459,7 @@ def main():
         except GradientExchangeError as e:     # the process group is aborted: leave non-zero, torchrun takes the job down
             exit_on_exchange_failure(e)
         opt.step()
-        return loss
+        return loss, logits, stats
 
     def barrier():
         if dp:
@@ -417,14 +478,16 @@ def main():
     # HIP-event brackets around every launch of the TIMED steps cost the host two event records per launch (~800 per step): opt-in
     if args.profile_timed:
         L.check(L.lib().octseg_profile_start())
-    sampler = PowerSampler(dev) if rank == 0 else None
+    sampler = PowerSampler(dev) if (rank == 0 and args.full) else None
     if sampler is not None:
         sampler.start()
     t0 = time.perf_counter()
     enq = 0.0
-    for _ in range(args.steps):
+    for i in range(args.steps):
         te = time.perf_counter()
-        loss = step()
+        if i == args.steps - 1:
+            restore_seeded_state()
+        loss, logits, stats = step()
         enq += time.perf_counter() - te      # host time to ENQUEUE a step (no synchronisation inside): how far the host runs ahead
     barrier()
     dt = time.perf_counter() - t0
@@ -433,21 +496,29 @@ def main():
     if args.profile_timed:
         L.check(L.lib().octseg_profile_stop(prof))
     loss_val = float(loss.item())
-    # Roofline pass (untimed, after the measured steps): the same step with every launch on one stream, so that the
-    # HIP-event bracket of a launch is the duration of that kernel alone.  In the timed steps the weight gradients and
-    # part of the decoder run on a side stream; brackets taken there also contain the time a kernel shares the chip.
-    prof_alone = (C.c_double * 12)()
-    n_alone = 2
-    net.use_train_graph = False          # the roofline pass brackets every launch: eager, one stream
-    L.check(L.lib().octseg_debug_set_serial(1))
-    step()
-    barrier()
-    L.check(L.lib().octseg_profile_start())
-    for _ in range(n_alone):
+    if args.dump_outputs and rank == 0:
+        # what the step hands its caller: loss, logits, Dice counts [B, C, 4] (tp, fp, fn, tn), and what it leaves on the net -- the
+        # gradients, the weights after the optimizer step and the BatchNorm running statistics (the last three as a fixed sample
+        # when larger than the cap; the logits of the default workload, 7.9 M values, are written whole)
+        dump_outputs(args.dump_outputs, {'loss': (loss, 1), 'logits': (logits, 8 << 20), 'dice_stats': (stats, 1 << 18),
+                                         'grads': (net.arena.grad, 2 << 20), 'params': (net.arena.data, 2 << 20),
+                                         'bn_buffers': (net.bn_buffers, 1 << 20)})
+    if args.full:
+        # Roofline pass (untimed, after the measured steps): the same step with every launch on one stream, so that the
+        # HIP-event bracket of a launch is the duration of that kernel alone.  In the timed steps the weight gradients and
+        # part of the decoder run on a side stream; brackets taken there also contain the time a kernel shares the chip.
+        prof_alone = (C.c_double * 12)()
+        n_alone = 2
+        net.use_train_graph = False          # the roofline pass brackets every launch: eager, one stream
+        L.check(L.lib().octseg_debug_set_serial(1))
         step()
-    barrier()
-    L.check(L.lib().octseg_profile_stop(prof_alone))
-    L.check(L.lib().octseg_debug_set_serial(0))
+        barrier()
+        L.check(L.lib().octseg_profile_start())
+        for _ in range(n_alone):
+            step()
+        barrier()
+        L.check(L.lib().octseg_profile_stop(prof_alone))
+        L.check(L.lib().octseg_debug_set_serial(0))
     if world > 1:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
@@ -456,20 +527,6 @@ def main():
     if rank == 0:
         frames = global_batch * args.steps
         macs = net.fwd_macs(B, S, S) / B  # per frame
-        oms = [prof[0], prof[3], prof[6]]          # overlapped (timed) steps
-        ofl = [prof[1], prof[4], prof[7]]
-        ms = [prof_alone[0], prof_alone[3], prof_alone[6]]   # kernels alone (roofline pass)
-        fl = [prof_alone[1], prof_alone[4], prof_alone[7]]
-        nl = [prof_alone[2], prof_alone[5], prof_alone[8]]
-        tot_ms, tot_fl = sum(ms), sum(fl)
-        peak = 2500.0 if args.dtype == 'bf16' else 157.3
-        ach = tot_fl / (tot_ms * 1e-3) / 1e12 if tot_ms > 0 else 0.0
-        ex = [e / B for e in net.exec_macs(B, S, S)]          # per frame: forward, data gradient, weight gradient
-        ex_fl = tot_fl - n_alone * B * 2.0 * sum(macs - e for e in ex)          # FLOPs the bracketed launches executed
-        ach_ex = ex_fl / (tot_ms * 1e-3) / 1e12 if tot_ms > 0 else 0.0
-        executed = {'gflop_per_frame': round(2 * sum(ex) / 1e9, 1), 'share_of_algorithmic': round(sum(ex) / (3 * macs), 4) if macs > 0 else 1.0,
-                    'achieved': round(ach_ex, 2), 'frac': round(ach_ex / peak, 4),
-                    'by_class_gflop_per_frame': {k: round(2 * e / 1e9, 1) for k, e in zip(('fwd', 'dgrad', 'wgrad'), ex)}}
         out = {
             'metric': f'OCT frames/sec ({S}x{S}, {args.dtype}) fwd+bwd',
             'value': round(frames / dt, 3),
@@ -487,31 +544,51 @@ def main():
                        'global_batch': global_batch, 'parallelism': f'dp{world}', 'gmac_fwd_per_frame': round(macs / 1e9, 2)},
             'loss': round(loss_val, 6),
             'host_enqueue_ms_per_step': round(enq / args.steps * 1e3, 3),
-            'power': power,
-            'roofline': {
-                'bound': 'mfma', 'kernel': 'conv_mfma_kernel + conv3x3p_kernel + gemm1x1_kernel + thin_conv_kernel + wgrad_mfma_kernel + wgrad1x1_kernel + wgrad_convt16_kernel + thin_wgrad_kernel (implicit-GEMM conv fwd / dgrad / wgrad)',
-                'achieved': round(ach, 2), 'peak': peak, 'unit': 'TFLOP/s', 'frac': round(ach / peak, 4), 'traffic': None,
-                'launches_per_step': round(sum(nl) / n_alone, 1),
-                'avg_launch_ms': round(tot_ms / max(1.0, sum(nl)), 4),
-                'kernel_ms_per_step': round(tot_ms / n_alone, 3),
-                'by_class': {k: {'ms_per_step': round(m / n_alone, 3), 'tflops': round(f / (m * 1e-3) / 1e12, 2) if m > 0 else 0.0}
-                             for k, m, f in zip(('fwd', 'dgrad', 'wgrad'), ms, fl)},
-                'algorithmic_gflop_per_frame': round(6 * macs / 1e9, 1),
-                # `achieved` prices the reference graph's 6 x MACs.  Where the plan runs the decoder's nearest-x2 + 3x3 layers as a 4x4 stride-2
-                # kernel over the low-resolution map (same function of the same weights, 16 instead of 36 products per source pixel:
-                # octseg_plan_exec_macs) the matrix cores execute fewer FLOPs than that -- both are printed
-                'executed': executed,
-                'note': 'HIP-event brackets on the launch stream over an untimed pass of the same step with every launch on one '
-                        'stream (octseg_debug_set_serial): the duration of each kernel alone; rocprofv3 summary of that mode: '
-                        'profiles/r3_serial_kernel_stats.csv',
-                'overlapped': None if not args.profile_timed else {
-                    'note': 'the same brackets during the TIMED steps, where weight gradients and part of the decoder run on a '
-                            'side stream: durations include the time a kernel shares the chip (profiles/r3_bench_kernel_stats.csv)',
-                    'kernel_ms_per_step': round(sum(oms) / args.steps, 3),
-                    'achieved': round(sum(ofl) / (sum(oms) * 1e-3) / 1e12, 2) if sum(oms) > 0 else 0.0,
-                    'by_class': {k: {'ms_per_step': round(m / args.steps, 3), 'tflops': round(f / (m * 1e-3) / 1e12, 2) if m > 0 else 0.0}
-                                 for k, m, f in zip(('fwd', 'dgrad', 'wgrad'), oms, ofl)},
-                },
+        }
+        if args.train_graph:
+            out['config']['train_graph'] = 'forward + Dice + backward replayed as one hipGraph per step (octseg_net_train_step)'
+        if args.force_exchange:
+            out['config']['force_exchange'] = f'one-rank {args.backend} group: buffer broadcast + {args.allreduce_slices}-slice all-reduce issued beside the backward'
+        note(f'GPU: {out["value"]} frames/s, {out["ms_per_step"]} ms/step')
+    if rank == 0 and args.full:
+        oms = [prof[0], prof[3], prof[6]]          # overlapped (timed) steps
+        ofl = [prof[1], prof[4], prof[7]]
+        ms = [prof_alone[0], prof_alone[3], prof_alone[6]]   # kernels alone (roofline pass)
+        fl = [prof_alone[1], prof_alone[4], prof_alone[7]]
+        nl = [prof_alone[2], prof_alone[5], prof_alone[8]]
+        tot_ms, tot_fl = sum(ms), sum(fl)
+        peak = 2500.0 if args.dtype == 'bf16' else 157.3
+        ach = tot_fl / (tot_ms * 1e-3) / 1e12 if tot_ms > 0 else 0.0
+        ex = [e / B for e in net.exec_macs(B, S, S)]          # per frame: forward, data gradient, weight gradient
+        ex_fl = tot_fl - n_alone * B * 2.0 * sum(macs - e for e in ex)          # FLOPs the bracketed launches executed
+        ach_ex = ex_fl / (tot_ms * 1e-3) / 1e12 if tot_ms > 0 else 0.0
+        executed = {'gflop_per_frame': round(2 * sum(ex) / 1e9, 1), 'share_of_algorithmic': round(sum(ex) / (3 * macs), 4) if macs > 0 else 1.0,
+                    'achieved': round(ach_ex, 2), 'frac': round(ach_ex / peak, 4),
+                    'by_class_gflop_per_frame': {k: round(2 * e / 1e9, 1) for k, e in zip(('fwd', 'dgrad', 'wgrad'), ex)}}
+        out['power'] = power
+        out['roofline'] = {
+            'bound': 'mfma', 'kernel': 'conv_mfma_kernel + conv3x3p_kernel + gemm1x1_kernel + thin_conv_kernel + wgrad_mfma_kernel + wgrad1x1_kernel + wgrad_convt16_kernel + thin_wgrad_kernel (implicit-GEMM conv fwd / dgrad / wgrad)',
+            'achieved': round(ach, 2), 'peak': peak, 'unit': 'TFLOP/s', 'frac': round(ach / peak, 4), 'traffic': None,
+            'launches_per_step': round(sum(nl) / n_alone, 1),
+            'avg_launch_ms': round(tot_ms / max(1.0, sum(nl)), 4),
+            'kernel_ms_per_step': round(tot_ms / n_alone, 3),
+            'by_class': {k: {'ms_per_step': round(m / n_alone, 3), 'tflops': round(f / (m * 1e-3) / 1e12, 2) if m > 0 else 0.0}
+                         for k, m, f in zip(('fwd', 'dgrad', 'wgrad'), ms, fl)},
+            'algorithmic_gflop_per_frame': round(6 * macs / 1e9, 1),
+            # `achieved` prices the reference graph's 6 x MACs.  Where the plan runs the decoder's nearest-x2 + 3x3 layers as a 4x4 stride-2
+            # kernel over the low-resolution map (same function of the same weights, 16 instead of 36 products per source pixel:
+            # octseg_plan_exec_macs) the matrix cores execute fewer FLOPs than that -- both are printed
+            'executed': executed,
+            'note': 'HIP-event brackets on the launch stream over an untimed pass of the same step with every launch on one '
+                    'stream (octseg_debug_set_serial): the duration of each kernel alone; rocprofv3 summary of that mode: '
+                    'profiles/r3_serial_kernel_stats.csv',
+            'overlapped': None if not args.profile_timed else {
+                'note': 'the same brackets during the TIMED steps, where weight gradients and part of the decoder run on a '
+                        'side stream: durations include the time a kernel shares the chip (profiles/r3_bench_kernel_stats.csv)',
+                'kernel_ms_per_step': round(sum(oms) / args.steps, 3),
+                'achieved': round(sum(ofl) / (sum(oms) * 1e-3) / 1e12, 2) if sum(oms) > 0 else 0.0,
+                'by_class': {k: {'ms_per_step': round(m / args.steps, 3), 'tflops': round(f / (m * 1e-3) / 1e12, 2) if m > 0 else 0.0}
+                             for k, m, f in zip(('fwd', 'dgrad', 'wgrad'), oms, ofl)},
             },
         }
         if power and power.get('sclk_mhz'):   # the clock the card granted during the timed steps (sampled, not assumed)
@@ -520,10 +597,7 @@ def main():
                 'sclk_mhz': mhz, 'quoted_mhz': 2400, 'frac_at_granted_clock': round(ach / (peak * mhz / 2400.0), 4),
                 'note': 'hwmon freq1_input averaged over the timed steps of THIS run (a step alternates power-capped conv loops with HBM '
                         'sweeps, so the conv loops themselves run below this average); `peak` is the 2.4 GHz figure'}
-        if args.train_graph:
-            out['config']['train_graph'] = 'forward + Dice + backward replayed as one hipGraph per step (octseg_net_train_step)'
-        if args.force_exchange:
-            out['config']['force_exchange'] = f'one-rank {args.backend} group: buffer broadcast + {args.allreduce_slices}-slice all-reduce issued beside the backward'
+        note(f'MFMA kernels alone {ach:.1f} TFLOP/s')
         # HBM traffic of the MFMA kernels from the TCC counters (tools/collect_traffic.py, separate rocprofv3 --pmc passes)
         tpath = next((q for q in (os.path.join(ROOT, 'profiles', f'r{k}_traffic.json') for k in (6, 5, 4, 3, 2, 1)) if os.path.exists(q)), '')
         if os.path.exists(tpath) and args.workload == 'unetpp_r101_704' and B == 16 and args.dtype == 'bf16':
@@ -541,10 +615,10 @@ def main():
                 'kernel_ms_per_step': round(prof_alone[9] / n_alone, 3), 'launches_per_step': round(prof_alone[11] / n_alone, 1),
                 'algorithmic_gbytes_per_step': round(prof_alone[10] / n_alone / 1e9, 2),
                 'note': 'algorithmic bytes = every tensor these sweeps read or write, once; same untimed single-stream pass as roofline'}
-        note(f'GPU: {out["value"]} frames/s, {out["ms_per_step"]} ms/step; MFMA kernels {ach:.1f} TFLOP/s')
         if not args.no_cpu_baseline and world == 1:
             note('CPU baseline (oracle, 2 frames per step, fp32 + bf16 autocast) ...')
             out['cpu_baseline'] = cpu_baseline(arch, enc, classes, S)
+    if rank == 0:
         print(json.dumps(out), file=_RESULT_OUT, flush=True)
     if dp:
         torch.distributed.destroy_process_group()

@@ -1,15 +1,16 @@
 """GPU box: HBM traffic of the dominant kernel from the TCC counters, as MI355X_MICROARCH.md prescribes
 (separate --pmc passes for FETCH_SIZE and WRITE_SIZE; FETCH_SIZE doubled on gfx950 for wide coalesced reads;
 both are in KiB).  Writes profiles/<tag>_traffic.json, which bench.py reports as roofline.traffic.
-usage: collect_traffic.py <tag>      (run from the repo root, under gpurun; NOT under rocprofv3 itself)"""
+usage: collect_traffic.py <tag>      (run from the repo root; NOT under rocprofv3 itself; rocprofv3 output goes under $OUT, default out/)"""
 import csv, glob, json, os, subprocess, sys, collections
 tag = sys.argv[1] if len(sys.argv) > 1 else 'r1'
 os.environ['TMPDIR'] = '/tmp'
 res = {}
+OUT = os.environ.get('OUT', 'out')
 for ctr in ('FETCH_SIZE', 'WRITE_SIZE'):
-    out = f'gpurun_out/pmc_{tag}_{ctr}'
+    out = f'{OUT}/pmc_{tag}_{ctr}'
     subprocess.run(['rocprofv3', '--pmc', ctr, '--output-format', 'csv', '-d', out, '--', 'python3', 'bench.py', '--steps', '1',
-                    '--warmup', '1', '--no-cpu-baseline'], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+                    '--warmup', '1', '--full', '--no-cpu-baseline'], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     f = glob.glob(f'{out}/*/*counter_collection.csv')[0]
     agg = collections.defaultdict(lambda: [0.0, 0])
     for r in csv.DictReader(open(f)):
@@ -31,6 +32,6 @@ summary = {'kernels': rows,
 summary['mfma_family']['hbm_bytes_per_step'] = summary['mfma_family']['hbm_bytes_per_launch'] * tot_l / 5.0
 os.makedirs('profiles', exist_ok=True)
 json.dump(summary, open(f'profiles/{tag}_traffic.json', 'w'), indent=1)
-os.makedirs('gpurun_out', exist_ok=True)
-json.dump(summary, open(f'gpurun_out/{tag}_traffic.json', 'w'), indent=1)
+os.makedirs(OUT, exist_ok=True)
+json.dump(summary, open(f'{OUT}/{tag}_traffic.json', 'w'), indent=1)
 print(json.dumps(summary['mfma_family']))

@@ -5,7 +5,7 @@ out=gpurun_out/tied_ab.txt; : > $out
 for t in $modes; do
   [ "$t" = "-" ] && t="0"
   echo "== OCTSEG_TIED=$t $*" >> $out
-  OCTSEG_TIED=$t python bench.py --no-cpu-baseline "$@" 2>/dev/null | python -c "
+  OCTSEG_TIED=$t python bench.py --full --no-cpu-baseline "$@" 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):
