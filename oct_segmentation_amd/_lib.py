@@ -96,6 +96,11 @@ LOSS_KINDS = {'dice': 0, 'bce': 1, 'dice+bce': 2}
 SLICE_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t)
 SYMBOLS['octseg_net_backward_sliced'] = (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_float, _P, C.c_int, _P, SLICE_CB, _P])
 
+# uint8 frames / masks -> float32 NCHW batch (csrc/ingest.hip)
+SYMBOLS['octseg_ingest_image'] = (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P])
+SYMBOLS['octseg_ingest_mask'] = (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P])
+SYMBOLS['octseg_debug_set_ingest_variant'] = (C.c_int, [C.c_int])
+
 _lib = None
 
 

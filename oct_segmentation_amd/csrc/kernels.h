@@ -298,6 +298,14 @@ constexpr int AUG_NPARAM = 36;
 hipError_t launch_augment(const float* img, const float* mask, float* img_out, float* mask_out, const float* params, int B, int C, int H,
                           int W, hipStream_t st);
 
+// uint8 frames / masks -> the nets' float32 NCHW batch (ingest.hip): cv2.resize's 8-bit INTER_LINEAR (INTER_AREA at exactly 2x in both axes) and
+// INTER_NEAREST + class-channel select, from host-made tap tables.  variant 0 = the shipped kernels (ingest_image_kernel, ingest_mask_kernel),
+// 1 = the one-thread-per-pixel gather forms (measurement yardstick)
+hipError_t launch_ingest_image(const uint8_t* src, int B, int Hs, int Ws, int swap_rb, float* out, int Hd, int Wd, const int* xtab,
+                               const int* ytab, int variant, hipStream_t st);
+hipError_t launch_ingest_mask(const uint8_t* src, int B, int Hs, int Ws, int Cs, const int* ch_ids, int C, float* out, int Hd, int Wd,
+                              const int* rows, const int* cols, int variant, hipStream_t st);
+
 // fused optimizers over the flat fp32 arenas
 struct OptArgs {
   float* p; const float* g; float* m; float* v; size_t n;

@@ -2823,6 +2823,32 @@ int octseg_mask_assemble(const float* logits, int N, int classes, int H, int W, 
   return OCTSEG_OK;
 }
 
+// The input half of the pipeline (dataset.py:108-127, data/utils.py:159-166): see ingest.hip.  Enqueue only.
+static int g_ingest_variant = 0;   // octseg_debug_set_ingest_variant
+int octseg_debug_set_ingest_variant(int variant) {
+  if (variant != 0 && variant != 1) return fail(OCTSEG_BAD_ARG, "ingest variant must be 0 (staged) or 1 (per-pixel gather)");
+  g_ingest_variant = variant;
+  return OCTSEG_OK;
+}
+
+int octseg_ingest_image(const uint8_t* src, int B, int src_h, int src_w, int swap_rb, float* out, int dst_h, int dst_w, const int* xtab,
+                        const int* ytab, void* stream) {
+  if (!src || !out || !xtab || !ytab) return fail(OCTSEG_BAD_ARG, "null argument");
+  if (B <= 0 || src_h <= 0 || src_w <= 0 || dst_h <= 0 || dst_w <= 0) return fail(OCTSEG_BAD_SHAPE, "ingest_image: empty batch or frame");
+  HIPCHK(launch_ingest_image(src, B, src_h, src_w, swap_rb != 0, out, dst_h, dst_w, xtab, ytab, g_ingest_variant, (hipStream_t)stream));
+  return OCTSEG_OK;
+}
+
+int octseg_ingest_mask(const uint8_t* src, int B, int src_h, int src_w, int src_channels, const int* channel_ids, int C, float* out, int dst_h,
+                       int dst_w, const int* row_index, const int* col_index, void* stream) {
+  if (!src || !out || !channel_ids || !row_index || !col_index) return fail(OCTSEG_BAD_ARG, "null argument");
+  if (B <= 0 || src_h <= 0 || src_w <= 0 || src_channels <= 0 || C <= 0 || dst_h <= 0 || dst_w <= 0)
+    return fail(OCTSEG_BAD_SHAPE, "ingest_mask: empty batch, frame or class list");
+  HIPCHK(launch_ingest_mask(src, B, src_h, src_w, src_channels, channel_ids, C, out, dst_h, dst_w, row_index, col_index, g_ingest_variant,
+                            (hipStream_t)stream));
+  return OCTSEG_OK;
+}
+
 int octseg_dice_forward(octseg_plan* p, void* workspace, const float* logits, const float* target, float* loss,
                         long long* stats, void* stream) {
   if (!p || !workspace || !logits || !target || !loss) return fail(OCTSEG_BAD_ARG, "null argument");

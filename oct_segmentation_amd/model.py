@@ -199,8 +199,14 @@ class OCTSegmentationModel(nn.Module):
         return out.cpu().numpy().round()
 
     def predict_logits(self, images):
-        """The device half of ``predict``: NHWC numpy in, NCHW float32 logits on the GPU out (no host round trip)."""
-        x = torch.as_tensor(np.ascontiguousarray(images.transpose((0, 3, 1, 2))), dtype=torch.float32).to(self.model.device)
+        """The device half of ``predict``: NHWC numpy in, NCHW float32 logits on the GPU out (no host round trip).  A float32 NCHW CUDA
+        tensor (what ``ingest.resize_image_u8`` makes) is taken as it is."""
+        if torch.is_tensor(images):
+            if not (images.is_cuda and images.dtype == torch.float32 and images.dim() == 4):
+                raise ValueError('predict_logits() takes NHWC numpy frames or a float32 NCHW CUDA tensor')
+            x = images.to(self.model.device).contiguous()
+        else:
+            x = torch.as_tensor(np.ascontiguousarray(images.transpose((0, 3, 1, 2))), dtype=torch.float32).to(self.model.device)
         was_training = self.model.training
         try:
             return self.model(x, normalize=False)

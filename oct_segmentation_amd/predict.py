@@ -127,9 +127,34 @@ def pil_nearest_index(src, dst):
     return out
 
 
+def _upload_frames_u8(images, device):
+    """The PIL frames as uint8 RGB on the device, uploaded once: one stacked [n,H,W,3] tensor when they share a size, else a list of
+    [1,H,W,3] tensors."""
+    arrs = [np.array(img.convert('RGB')) for img in images]
+    if all(a.shape == arrs[0].shape for a in arrs):
+        return torch.from_numpy(np.stack(arrs)).to(device)
+    return [torch.from_numpy(a)[None].to(device) for a in arrs]
+
+
+def _resize_frames_on_device(frames, lo, hi, size):
+    """preprocessing_img of frames lo..hi-1 on the GPU (octseg_ingest_image, RGB -> BGR planes): float32 [hi - lo, 3, size, size]."""
+    from . import ingest
+    if torch.is_tensor(frames):
+        return ingest.resize_image_u8(frames[lo:hi], size, swap_rb=True)
+    hi = min(hi, len(frames))
+    out = torch.empty((hi - lo, 3, size, size), dtype=torch.float32, device=frames[lo].device)
+    for k in range(lo, hi):
+        ingest.resize_image_u8(frames[k], size, swap_rb=True, out=out[k - lo:k - lo + 1])
+    return out
+
+
 def segment(images, masks, output_size, classes, models_dir, device='cuda', batch_size=8, compute_dtype=torch.bfloat16,
-            use_graph=False):
+            use_graph=False, device_preprocess=False):
     """predict.py:61-101.  images: list of PIL images; masks: list of zero arrays [H_out, W_out, 4].
+
+    ``device_preprocess`` (default off: the host path above stays what every existing caller gets): every frame is uploaded ONCE as
+    uint8 RGB and resized to each model's ``input_size`` on the GPU (``ingest.resize_image_u8``, equal to ``preprocessing_img`` sample
+    for sample), batch by batch; the nets take those tensors as they are -- no numpy resize and no float32 host-to-device copy.
 
     Every model runs once (the reference runs FC_LC once per class), in batches (with ``use_graph`` the nets' replayed forwards side by
     side); thresholding, the nearest resize to
@@ -142,11 +167,14 @@ def segment(images, masks, output_size, classes, models_dir, device='cuda', batc
     oh, ow = masks[0].shape[0], masks[0].shape[1]
     stack = torch.zeros((n, oh, ow, 4), dtype=torch.float32, device=device)
     cache, tables, loaded = {}, {}, {}
+    frames_u8 = _upload_frames_u8(images, device) if device_preprocess else None
     for class_name in classes:     # every distinct model once: weights and the preprocessed frames at that model's input size
         model_dir = os.path.join(models_dir, MODELS_META[class_name]['model_dir'])
         if model_dir not in loaded:
             model, cfg = load_model(model_dir, device, compute_dtype, use_graph=use_graph)
-            loaded[model_dir] = (model, np.array([preprocessing_img(img, cfg['input_size']) for img in images]))
+            # host path: the preprocessed frames [n, S, S, 3]; device path: just S, the frames are resized per batch below
+            loaded[model_dir] = (model, int(cfg['input_size']) if device_preprocess else
+                                 np.array([preprocessing_img(img, cfg['input_size']) for img in images]))
     parts = {d: [] for d in loaded}
     for i in range(0, n, batch_size):
         if use_graph:
@@ -154,13 +182,17 @@ def segment(images, masks, output_size, classes, models_dir, device='cuda', batc
             # at one frame per step a single net fills a fraction of the chip (SegNet.forward_async)
             handles = {}
             for d, (model, batch) in loaded.items():
-                x = torch.as_tensor(np.ascontiguousarray(batch[i:i + batch_size].transpose((0, 3, 1, 2))), dtype=torch.float32).to(model.model.device)
+                if device_preprocess:
+                    x = _resize_frames_on_device(frames_u8, i, i + batch_size, batch)
+                else:
+                    x = torch.as_tensor(np.ascontiguousarray(batch[i:i + batch_size].transpose((0, 3, 1, 2))), dtype=torch.float32).to(model.model.device)
                 handles[d] = model.model.eval().forward_async(x, normalize=False)
             for d, h in handles.items():
                 parts[d].append(loaded[d][0].model.forward_join(h))
         else:
             for d, (model, batch) in loaded.items():
-                parts[d].append(model.predict_logits(batch[i:i + batch_size]))
+                parts[d].append(model.predict_logits(_resize_frames_on_device(frames_u8, i, i + batch_size, batch) if device_preprocess
+                                                     else batch[i:i + batch_size]))
     for d in loaded:
         cache[d] = torch.cat(parts[d], dim=0)
     del loaded

@@ -1,6 +1,7 @@
 """Thin training loop standing in for ``pl.Trainer.fit`` in ``src/models/smp/train.py:25-134`` (Lightning,
-W&B and the file dataset are out of scope): builds ``OCTSegmentationModel`` from a train.yaml-style config,
-steps it on batches from any iterable of ``(img [B,3,S,S] f32 0..255 BGR, mask [B,C,S,S] f32)`` and writes the
+W&B are out of scope): builds ``OCTSegmentationModel`` from a train.yaml-style config,
+steps it on batches from any iterable of ``(img [B,3,S,S] f32 0..255 BGR, mask [B,C,S,S] f32)`` (``dataset.train_batches`` makes one
+from the reference's file tree) and writes the
 reference's ``config.json`` + ``weights.ckpt`` pair.  Data parallel when launched under torchrun."""
 import json
 import os
