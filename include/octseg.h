@@ -31,6 +31,8 @@
  *                                      (dataset.py:111-118,125)
  *   octseg_mask_assemble               the per-frame epilogue of segment(): threshold, cv2 INTER_NEAREST resize to output_size,
  *                                      write into mask[:, :, CLASS_ID - 1] (src/predict.py:92-100, data/utils.py:16-33)
+ *   octseg_render_results              save_results: closing, ring, blur, two alpha pastes per class into the frame, the flat colour mask
+ *                                      (src/data/utils.py:195-235, get_img_mask_union_pil src/models/smp/utils.py:203-213)
  *   octseg_plan_set_graph              (serving option, no reference counterpart) eval forwards of predict()
  *                                      (model.py:183-200) replayed as one hipGraph
  *   octseg_plan_params_changed         optimizer.step() / load_state_dict() side effect: weight images are stale
@@ -214,6 +216,27 @@ int octseg_ingest_mask(const uint8_t* src, int B, int src_h, int src_w, int src_
 /* Measurement aid: 0 (default) = the shipped ingest kernels, 1 = their one-thread-per-output-pixel gather forms (tools/bench_ingest.py times
  * one beside the other).  Same results. */
 int octseg_debug_set_ingest_variant(int variant);
+
+/* Output half of the pipeline: save_results (reference src/data/utils.py:195-235) with get_img_mask_union_pil (src/models/smp/utils.py:203-213)
+ * and the class colours / ids of src/data/utils.py:16-43, for a whole batch in ONE launch.
+ * stack: f32 [N][H][W][stack_channels], values 0 / 1 (what octseg_mask_assemble writes; any value != 0 counts as set); frames: uint8
+ * [N][H][W][3] RGB, the frame already at output size; class_channels: device int32 [C] stack channel of every class (CLASS_IDS[name] - 1; ids
+ * outside [0, stack_channels) are clamped on the device, as in octseg_ingest_mask); class_rgb: device uint8 [C][3]; alpha_table: device uint8
+ * [257]; overlay / color_mask: uint8 [N][H][W][3], must not overlap the inputs.  Per frame, for class c = 0..C-1 IN ORDER, m0 = stack[..., ch_c] != 0:
+ *   m    = erode^it(dilate^it(m0)), it = close_iterations, element = cv2.getStructuringElement(MORPH_ELLIPSE, (5, 5)) (row widths 1,5,5,5,1);
+ *   ring = dilate(m, ellipse(7, 7)) and not erode(m, ellipse(7, 7)) (row widths 1,5,7,7,7,5,1).  OpenCV's morphology border: positions outside
+ *          the frame do not take part -- 0 for every dilation, 1 for every erosion, at every one of the iterated stages;
+ *   k    = sum over the 5 x 5 window of (1,4,6,4,1) x (1,4,6,4,1) * m with BORDER_REFLECT_101 = 256 * cv2.GaussianBlur(m, (5, 5), 0), an integer 0..256;
+ *   overlay = paste(paste(overlay, rgb_c, alpha_table[k]), rgb_c, ring ? ring_alpha : 0), starting from frames, with PIL's
+ *          paste(in, col, a) = ((t >> 8) + t) >> 8, t = in * (255 - a) + col * a + 128 per channel;
+ *   color_mask = rgb_c where m0 is set (the RAW mask), starting from (128, 128, 128); later classes overwrite earlier ones.
+ * The host mirror (oct_segmentation_amd/postprocess.py) fills alpha_table[k] = uint8(k / 256 * 64 * 0.85 * 255) and ring_alpha = uint8(255 * 0.85 * 255)
+ * with the reference's float64 order of operations and numpy's wrapping cast (alpha_table[256] = 48, ring_alpha = 231).  Integer arithmetic
+ * throughout: both outputs EQUAL the reference's, no tolerance.
+ * Enqueue only.  Null pointer: OCTSEG_BAD_ARG; N, H, W, C, stack_channels <= 0, C > 16 or close_iterations outside 1..3: OCTSEG_BAD_SHAPE. */
+int octseg_render_results(const float* stack, const uint8_t* frames, int N, int H, int W, int stack_channels, const int* class_channels,
+                          const uint8_t* class_rgb, int C, const uint8_t* alpha_table, int ring_alpha, int close_iterations, uint8_t* overlay,
+                          uint8_t* color_mask, void* stream);
 
 /* Criterion evaluated by octseg_dice_forward / octseg_net_train_step and differentiated by the backward entry points.
  * OCTSEG_LOSS_DICE (default) = smp.losses.DiceLoss(MULTILABEL_MODE, from_logits=True), the reference's (model.py:55);

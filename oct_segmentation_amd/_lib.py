@@ -100,6 +100,8 @@ SYMBOLS['octseg_net_backward_sliced'] = (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_f
 SYMBOLS['octseg_ingest_image'] = (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P])
 SYMBOLS['octseg_ingest_mask'] = (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P])
 SYMBOLS['octseg_debug_set_ingest_variant'] = (C.c_int, [C.c_int])
+# float32 mask stack + uint8 frames -> uint8 overlay + colour mask (csrc/render.hip)
+SYMBOLS['octseg_render_results'] = (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P])
 
 _lib = None
 

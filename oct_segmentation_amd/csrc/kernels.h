@@ -306,6 +306,11 @@ hipError_t launch_ingest_image(const uint8_t* src, int B, int Hs, int Ws, int sw
 hipError_t launch_ingest_mask(const uint8_t* src, int B, int Hs, int Ws, int Cs, const int* ch_ids, int C, float* out, int Hd, int Wd,
                               const int* rows, const int* cols, int variant, hipStream_t st);
 
+// save_results on the GPU (render.hip): closing, ring, blur, the two pastes per class and the colour mask in one launch; uint8 HWC in and out
+hipError_t launch_render_results(const float* stack, const uint8_t* frames, int N, int H, int W, int SC, const int* class_ch,
+                                 const uint8_t* class_rgb, int C, const uint8_t* alpha_tab, int ring_alpha, int iters, uint8_t* overlay,
+                                 uint8_t* cmask, hipStream_t st);
+
 // fused optimizers over the flat fp32 arenas
 struct OptArgs {
   float* p; const float* g; float* m; float* v; size_t n;

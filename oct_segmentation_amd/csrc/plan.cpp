@@ -2849,6 +2849,19 @@ int octseg_ingest_mask(const uint8_t* src, int B, int src_h, int src_w, int src_
   return OCTSEG_OK;
 }
 
+// The output half of the pipeline (data/utils.py:195-235, models/smp/utils.py:203-213): see render.hip.  Enqueue only.
+int octseg_render_results(const float* stack, const uint8_t* frames, int N, int H, int W, int stack_channels, const int* class_channels,
+                          const uint8_t* class_rgb, int C, const uint8_t* alpha_table, int ring_alpha, int close_iterations, uint8_t* overlay,
+                          uint8_t* color_mask, void* stream) {
+  if (!stack || !frames || !class_channels || !class_rgb || !alpha_table || !overlay || !color_mask) return fail(OCTSEG_BAD_ARG, "null argument");
+  if (N <= 0 || H <= 0 || W <= 0 || stack_channels <= 0 || C <= 0 || C > 16)
+    return fail(OCTSEG_BAD_SHAPE, "render_results: empty batch or frame, or not 1..16 classes");
+  if (close_iterations < 1 || close_iterations > 3) return fail(OCTSEG_BAD_SHAPE, "render_results: close_iterations must be 1, 2 or 3");
+  HIPCHK(launch_render_results(stack, frames, N, H, W, stack_channels, class_channels, class_rgb, C, alpha_table, ring_alpha, close_iterations,
+                               overlay, color_mask, (hipStream_t)stream));
+  return OCTSEG_OK;
+}
+
 int octseg_dice_forward(octseg_plan* p, void* workspace, const float* logits, const float* target, float* loss,
                         long long* stats, void* stream) {
   if (!p || !workspace || !logits || !target || !loss) return fail(OCTSEG_BAD_ARG, "null argument");

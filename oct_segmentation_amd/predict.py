@@ -148,23 +148,16 @@ def _resize_frames_on_device(frames, lo, hi, size):
     return out
 
 
-def segment(images, masks, output_size, classes, models_dir, device='cuda', batch_size=8, compute_dtype=torch.bfloat16,
-            use_graph=False, device_preprocess=False):
-    """predict.py:61-101.  images: list of PIL images; masks: list of zero arrays [H_out, W_out, 4].
-
-    ``device_preprocess`` (default off: the host path above stays what every existing caller gets): every frame is uploaded ONCE as
-    uint8 RGB and resized to each model's ``input_size`` on the GPU (``ingest.resize_image_u8``, equal to ``preprocessing_img`` sample
-    for sample), batch by batch; the nets take those tensors as they are -- no numpy resize and no float32 host-to-device copy.
-
-    Every model runs once (the reference runs FC_LC once per class), in batches (with ``use_graph`` the nets' replayed forwards side by
-    side); thresholding, the nearest resize to
-    ``output_size`` and the 4-channel mask assembly happen on the GPU (``octseg_mask_assemble``); one D2H copy of the
-    assembled 0/1 stack at the end instead of one logits tensor per frame and class."""
+def segment_stack(images, output_size, classes, models_dir, device='cuda', batch_size=8, compute_dtype=torch.bfloat16, use_graph=False,
+                  device_preprocess=False):
+    """``segment()`` up to and including the mask assembly, with the result left where it was made: the float32 0 / 1 stack
+    [n, output_size[0], output_size[1], 4] on the device (channel = CLASS_ID - 1; classes that were not asked for stay 0).  What
+    ``postprocess.save_results`` / ``render_results`` take; ``segment()`` copies it to the host arrays of the reference's interface."""
     from . import _lib as L
     n = len(images)
     # cv2 sizes are (width, height); the reference allocates masks as [output_size[0], output_size[1], 4] and resizes
     # to tuple(output_size): the assignment into mask[:, :, c] only works for square sizes, and so do the extents below
-    oh, ow = masks[0].shape[0], masks[0].shape[1]
+    oh, ow = int(output_size[0]), int(output_size[1])
     stack = torch.zeros((n, oh, ow, 4), dtype=torch.float32, device=device)
     cache, tables, loaded = {}, {}, {}
     frames_u8 = _upload_frames_u8(images, device) if device_preprocess else None
@@ -208,6 +201,23 @@ def segment(images, masks, output_size, classes, models_dir, device='cuda', batc
         rows, cols = tables[key]
         L.check(L.lib().octseg_mask_assemble(L.ptr(z), n, z.shape[1], z.shape[2], z.shape[3], int(ch), L.ptr(stack), oh, ow, 4,
                                              CLASS_IDS[class_name] - 1, L.ptr(rows), L.ptr(cols), L.stream_ptr()))
+    return stack
+
+
+def segment(images, masks, output_size, classes, models_dir, device='cuda', batch_size=8, compute_dtype=torch.bfloat16,
+            use_graph=False, device_preprocess=False):
+    """predict.py:61-101.  images: list of PIL images; masks: list of zero arrays [H_out, W_out, 4].
+
+    ``device_preprocess`` (default off: the host path above stays what every existing caller gets): every frame is uploaded ONCE as
+    uint8 RGB and resized to each model's ``input_size`` on the GPU (``ingest.resize_image_u8``, equal to ``preprocessing_img`` sample
+    for sample), batch by batch; the nets take those tensors as they are -- no numpy resize and no float32 host-to-device copy.
+
+    Every model runs once (the reference runs FC_LC once per class), in batches (with ``use_graph`` the nets' replayed forwards side by
+    side); thresholding, the nearest resize to
+    ``output_size`` and the 4-channel mask assembly happen on the GPU (``octseg_mask_assemble``); one D2H copy of the
+    assembled 0/1 stack at the end instead of one logits tensor per frame and class."""
+    stack = segment_stack(images, masks[0].shape[:2], classes, models_dir, device=device, batch_size=batch_size, compute_dtype=compute_dtype,
+                          use_graph=use_graph, device_preprocess=device_preprocess)
     host = stack.cpu().numpy()
     for i, mask in enumerate(masks):
         for class_name in classes:
@@ -223,3 +233,53 @@ def data_processing(image_paths, output_size):
         images.append(Image.open(p).resize(tuple(output_size)))
         masks.append(np.zeros((output_size[0], output_size[1], 4)))
     return images, masks
+
+
+def _image_paths(data_path):
+    """data/utils.py:175-178: one file, or the directory's ``*.[pj][np][ge]*`` (png, jpg, jpeg ...)."""
+    if os.path.isfile(data_path):
+        return [data_path]
+    from glob import glob
+    return glob(f'{data_path}/*.[pj][np][ge]*')
+
+
+def main(argv=None):
+    """src/predict.py:109-149 from ``configs/predict.yaml`` (``key=value`` overrides as with hydra): data_processing -> segment -> save_results,
+    two PNGs per frame in ``save_dir``.  The frames go up once as uint8, the masks stay on the device from the nets to the rendering kernel
+    (``segment_stack`` -> ``postprocess.save_results``); what comes back is the uint8 overlay and colour mask, 6 bytes per pixel instead of the
+    16 of the float32 stack.  Extra keys: ``compute_dtype`` (bf16 | fp16 | fp32), ``batch_size``, ``use_graph``, ``close_iterations``."""
+    import logging
+    import sys
+    import time
+    from .config import load_config
+    from .postprocess import save_results
+    log = logging.getLogger('oct_segmentation_amd.predict')
+    if not logging.getLogger().handlers:
+        logging.basicConfig(level=logging.INFO, format='[%(asctime)s][%(name)s][%(levelname)s] - %(message)s')
+    cfg = load_config('predict', list(sys.argv[1:] if argv is None else argv))
+    device = 'cuda' if cfg.get('device', 'auto') in ('auto', 'gpu', 'cuda') else cfg['device']
+    if not (str(device).startswith('cuda') and torch.cuda.is_available()):
+        raise RuntimeError(f'predict needs a GPU (device={cfg.get("device")!r}): there is no CPU path')
+    dtypes = {'bf16': torch.bfloat16, 'fp16': torch.float16, 'fp32': torch.float32}
+    start = time.time()
+    paths = _image_paths(str(cfg['data_dir']))
+    if not paths:
+        raise FileNotFoundError(f'no images under {cfg["data_dir"]}')
+    os.makedirs(str(cfg['save_dir']), exist_ok=True)
+    images, _ = data_processing(paths, cfg['output_size'])
+    names = [os.path.basename(p).split('.')[0] for p in paths]
+    log.info(f'Number of images: {len(names)}')
+    start_inference = time.time()
+    stack = segment_stack(images, cfg['output_size'], cfg['classes'], str(cfg['models_dir']), device=device,
+                          batch_size=int(cfg.get('batch_size', 8)), compute_dtype=dtypes[str(cfg.get('compute_dtype', 'bf16'))],
+                          use_graph=bool(cfg.get('use_graph', False)), device_preprocess=True)
+    torch.cuda.synchronize()
+    log.info(f'Prediction time: {time.time() - start_inference:.1f} s')
+    save_results(images, stack, names, cfg['classes'], str(cfg['save_dir']), close_iterations=int(cfg.get('close_iterations', 1)))
+    log.info(f'Overall computation time: {time.time() - start:.1f} s')
+    log.info('Complete')
+    return 0
+
+
+if __name__ == '__main__':
+    raise SystemExit(main())
