@@ -47,8 +47,10 @@ class BNInfo(C.Structure):
     _fields_ = [('name', C.c_char * 128), ('C', C.c_int), ('mean_offset', C.c_size_t), ('var_offset', C.c_size_t)]
 
 
-# every exported symbol with (restype, argtypes); tests check the library exports all of them
+# every exported symbol with (restype, argtypes), in the order of include/octseg.h; tests check the library exports all of them
 _P = C.c_void_p
+LOSS_KINDS = {'dice': 0, 'bce': 1, 'dice+bce': 2}
+SLICE_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t)
 SYMBOLS = {
     'octseg_version': (C.c_int, []),
     'octseg_last_error': (C.c_char_p, []),
@@ -67,14 +69,30 @@ SYMBOLS = {
     'octseg_profile_start': (C.c_int, []),
     'octseg_profile_stop': (C.c_int, [C.POINTER(C.c_double)]),
     'octseg_plan_params_changed': (C.c_int, [_P]),
+    'octseg_plan_set_dropout': (C.c_int, [_P, _P]),
+    'octseg_plan_set_drop_connect': (C.c_int, [_P, _P]),
+    'octseg_plan_num_drop_connect': (C.c_int, [_P]),
+    'octseg_plan_drop_connect_rate': (C.c_float, [_P, C.c_int]),
     'octseg_plan_set_graph': (C.c_int, [_P, C.c_int]),
-    'octseg_augment': (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
-    'octseg_mask_assemble': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     'octseg_net_forward': (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                      C.c_int, _P]),
+    'octseg_augment': (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    'octseg_mask_assemble': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    # uint8 frames / masks -> float32 NCHW batch (csrc/ingest.hip)
+    'octseg_ingest_image': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P]),
+    'octseg_ingest_mask': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P]),
+    'octseg_debug_set_ingest_variant': (C.c_int, [C.c_int]),
+    # float32 mask stack + uint8 frames -> uint8 overlay + colour mask (csrc/render.hip)
+    'octseg_render_results': (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P]),
+    'octseg_plan_set_loss': (C.c_int, [_P, C.c_int]),
     'octseg_dice_forward': (C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
     'octseg_net_backward': (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_float, _P]),
+    'octseg_net_train_step': (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                        C.c_float, _P]),
+    'octseg_plan_set_train_graph': (C.c_int, [_P, C.c_int]),
+    'octseg_net_backward_sliced': (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_float, _P, C.c_int, _P, SLICE_CB, _P]),
     'octseg_optim_step': (C.c_int, [C.c_int, _P, _P, _P, _P, C.c_size_t, C.c_float, C.c_float, C.c_int, C.c_float, _P]),
+    'octseg_set_deterministic': (C.c_int, [C.c_int]),
     'octseg_debug_set_stamp': (C.c_int, [_P]),
     'octseg_debug_set_serial': (C.c_int, [C.c_int]),
     'octseg_conv2d_scratch_bytes': (C.c_size_t, [C.c_int] * 8),
@@ -82,26 +100,6 @@ SYMBOLS = {
     'octseg_conv2d_backward_data': (C.c_int, [C.c_int, _P, _P, _P] + [C.c_int] * 10 + [_P, _P]),
     'octseg_conv2d_backward_weight': (C.c_int, [C.c_int, _P, _P, _P] + [C.c_int] * 10 + [_P]),
 }
-
-SYMBOLS['octseg_set_deterministic'] = (C.c_int, [C.c_int])
-SYMBOLS['octseg_plan_set_dropout'] = (C.c_int, [_P, _P])
-SYMBOLS['octseg_net_train_step'] = (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float),
-                                              C.c_float, _P])
-SYMBOLS['octseg_plan_set_train_graph'] = (C.c_int, [_P, C.c_int])
-SYMBOLS['octseg_plan_set_loss'] = (C.c_int, [_P, C.c_int])
-SYMBOLS['octseg_plan_set_drop_connect'] = (C.c_int, [_P, _P])
-SYMBOLS['octseg_plan_num_drop_connect'] = (C.c_int, [_P])
-SYMBOLS['octseg_plan_drop_connect_rate'] = (C.c_float, [_P, C.c_int])
-LOSS_KINDS = {'dice': 0, 'bce': 1, 'dice+bce': 2}
-SLICE_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t)
-SYMBOLS['octseg_net_backward_sliced'] = (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_float, _P, C.c_int, _P, SLICE_CB, _P])
-
-# uint8 frames / masks -> float32 NCHW batch (csrc/ingest.hip)
-SYMBOLS['octseg_ingest_image'] = (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P])
-SYMBOLS['octseg_ingest_mask'] = (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P])
-SYMBOLS['octseg_debug_set_ingest_variant'] = (C.c_int, [C.c_int])
-# float32 mask stack + uint8 frames -> uint8 overlay + colour mask (csrc/render.hip)
-SYMBOLS['octseg_render_results'] = (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P])
 
 _lib = None
 

@@ -4,12 +4,16 @@
 //
 // Nothing is executed: a "launch" checks its geometry against what gfx950 accepts (non-empty grid, block of 64..1024 threads in whole
 // waves, dynamic LDS <= 160 KiB) and is counted; memsets / copies check that their device range lies inside a range the test registered
-// (dry_register_range) -- the fake arenas are address ranges that are never dereferenced.
+// (dry_register_range) -- the fake arenas are address ranges that are never dereferenced.  Every launch (kernel name, grid, block, dynamic
+// LDS, stream) and every memset / copy (offset inside its range, byte count) also goes into one running hash, dry_fingerprint(): two builds
+// that enqueue the same work in the same order on the same streams print the same value (evidence for a refactor, pinned by no test).
 #include <hip/hip_runtime_api.h>
 
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
+#include <string>
 #include <vector>
 
 namespace {
@@ -25,6 +29,15 @@ bool in_ranges(const void* p, size_t n) {
   for (auto& r : g_ranges) if (c >= r.lo && c + n <= r.hi) return true;
   return false;
 }
+size_t range_offset(const void* p, size_t n) {   // offset from the base of the registered range [p, p + n) falls in
+  const char* c = (const char*)p;
+  for (auto& r : g_ranges) if (c >= r.lo && c + n <= r.hi) return (size_t)(c - r.lo);
+  return ~(size_t)0;
+}
+std::map<const void*, std::string>& kernel_names() { static std::map<const void*, std::string> m; return m; }   // (filled by static initialisers of other files)
+unsigned long long g_hash = 0xcbf29ce484222325ull;   // 64-bit FNV-1a
+void hash_bytes(const void* p, size_t n) { for (size_t i = 0; i < n; ++i) { g_hash ^= ((const unsigned char*)p)[i]; g_hash *= 0x100000001b3ull; } }
+void hash_u64(unsigned long long v) { hash_bytes(&v, sizeof v); }
 void complain(const char* what) { fprintf(stderr, "hip_host_stubs: %s\n", what); ++g_errors; }
 }  // namespace
 
@@ -34,10 +47,13 @@ void dry_clear_ranges() { g_ranges.clear(); }
 unsigned long long dry_launches() { return g_launches; }
 unsigned long long dry_memops() { return g_memsets + g_copies; }
 unsigned long long dry_errors() { return g_errors; }
+unsigned long long dry_fingerprint() { return g_hash; }
 
 // ---- registration hooks emitted by clang for every translation unit with kernels
 void** __hipRegisterFatBinary(const void*) { static void* h = nullptr; return &h; }
-void __hipRegisterFunction(void**, const void*, char*, const char*, unsigned, void*, void*, void*, void*, int*) {}
+void __hipRegisterFunction(void**, const void* host_fn, char*, const char* device_name, unsigned, void*, void*, void*, void*, int*) {
+  kernel_names()[host_fn] = device_name;
+}
 void __hipUnregisterFatBinary(void**) {}
 hipError_t __hipPushCallConfiguration(dim3 grid, dim3 block, size_t shmem, hipStream_t st) {
   g_grid = grid; g_block = block; g_shmem = shmem; g_stream = st;
@@ -47,8 +63,13 @@ hipError_t __hipPopCallConfiguration(dim3* grid, dim3* block, size_t* shmem, hip
   *grid = g_grid; *block = g_block; *shmem = g_shmem; *st = g_stream;
   return hipSuccess;
 }
-hipError_t hipLaunchKernel(const void* fn, dim3 grid, dim3 block, void** args, size_t shmem, hipStream_t) {
+hipError_t hipLaunchKernel(const void* fn, dim3 grid, dim3 block, void** args, size_t shmem, hipStream_t st) {
   ++g_launches;
+  const std::string& name = kernel_names()[fn];
+  hash_bytes(name.data(), name.size());
+  for (unsigned long long v : {(unsigned long long)grid.x, (unsigned long long)grid.y, (unsigned long long)grid.z, (unsigned long long)block.x,
+                               (unsigned long long)block.y, (unsigned long long)block.z, (unsigned long long)shmem, (unsigned long long)(uintptr_t)st})
+    hash_u64(v);
   const unsigned long long threads = (unsigned long long)block.x * block.y * block.z;
   if (!fn || !args) complain("launch without a function or an argument list");
   if (grid.x == 0 || grid.y == 0 || grid.z == 0) complain("empty grid");
@@ -69,11 +90,13 @@ hipError_t hipGetLastError(void) { return hipSuccess; }
 const char* hipGetErrorString(hipError_t) { return "stub"; }
 hipError_t hipMemsetAsync(void* dst, int, size_t n, hipStream_t) {
   ++g_memsets;
+  hash_u64(range_offset(dst, n)); hash_u64(n);
   if (!in_ranges(dst, n)) complain("hipMemsetAsync outside every registered device range");
   return hipSuccess;
 }
 hipError_t hipMemcpyAsync(void* dst, const void* src, size_t n, hipMemcpyKind kind, hipStream_t) {
   ++g_copies;
+  hash_u64(in_ranges(dst, n) ? range_offset(dst, n) : range_offset(src, n)); hash_u64(n);
   if (kind == hipMemcpyHostToDevice) {
     if (!in_ranges(dst, n)) complain("H2D copy outside every registered device range");
     volatile unsigned char acc = 0;                      // touch the host source: ASan checks it is readable end to end

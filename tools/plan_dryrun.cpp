@@ -2,7 +2,7 @@
 //
 // Built by `make -C oct_segmentation_amd/csrc asan` from the HOST halves of every source (hipcc --cuda-host-only
 // -fsanitize=address,undefined): graph construction, workspace layout, tap tables, launch geometry, weight-image layouts, BN slab row
-// counts and the one-launch pack / BN job tables of csrc/plan.cpp -- ~1400 lines of index arithmetic -- run for every architecture x
+// counts and the one-launch pack / BN job tables of csrc/plan_geom.cpp and csrc/plan_build.cpp -- ~1400 lines of index arithmetic -- run for every architecture x
 // encoder pair at the smallest legal frame, the benchmark frame and a non-square one, in all three dtypes, with no kernel launched
 // (no GPU needed).  A subset of the plans is then driven through octseg_net_forward / _backward / _backward_sliced / octseg_optim_step and
 // the graph-captured eval forward against tools/hip_host_stubs.cpp, a recording stand-in for the HIP runtime that checks every launch
@@ -20,6 +20,7 @@ extern "C" void dry_clear_ranges();
 extern "C" unsigned long long dry_launches();
 extern "C" unsigned long long dry_memops();
 extern "C" unsigned long long dry_errors();
+extern "C" unsigned long long dry_fingerprint();
 
 namespace {
 int g_slices_seen = 0;
@@ -177,6 +178,7 @@ int main() {
   for (int dt = 0; dt < 3; ++dt) checksum += octseg_conv2d_scratch_bytes(dt, 2, 64, 64, 24, 40, 3, 3) + octseg_conv2d_scratch_bytes(dt, 1, 8, 8, 2048, 512, 1, 1);
   if (dry_errors() != 0) { fprintf(stderr, "%llu launch / memory-range violations\n", dry_errors()); return 8; }
   printf("plan_dryrun: %d plans built, %d of them run through forward / backward / optimizer with recording HIP stubs (%llu launches, %llu memory "
-         "operations checked) under ASan + UBSan, checksum %llu, 0 errors\n", plans, executed, dry_launches(), dry_memops(), checksum);
+         "operations checked) under ASan + UBSan, checksum %llu, 0 errors, launch fingerprint %016llx\n", plans, executed, dry_launches(), dry_memops(), checksum,
+         dry_fingerprint());
   return 0;
 }
