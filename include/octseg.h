@@ -33,6 +33,8 @@
  *                                      write into mask[:, :, CLASS_ID - 1] (src/predict.py:92-100, data/utils.py:16-33)
  *   octseg_render_results              save_results: closing, ring, blur, two alpha pastes per class into the frame, the flat colour mask
  *                                      (src/data/utils.py:195-235, get_img_mask_union_pil src/models/smp/utils.py:203-213)
+ *   octseg_stack_measure               the measurements of the app's get_analysis: set pixels per slice and class, and the ray walk of
+ *                                      calculate_object_thickness per slice, class and degree (src/app/tools/analysis.py:60-130,189,199-200)
  *   octseg_plan_set_graph              (serving option, no reference counterpart) eval forwards of predict()
  *                                      (model.py:183-200) replayed as one hipGraph
  *   octseg_plan_params_changed         optimizer.step() / load_state_dict() side effect: weight images are stale
@@ -237,6 +239,24 @@ int octseg_debug_set_ingest_variant(int variant);
 int octseg_render_results(const float* stack, const uint8_t* frames, int N, int H, int W, int stack_channels, const int* class_channels,
                           const uint8_t* class_rgb, int C, const uint8_t* alpha_table, int ring_alpha, int close_iterations, uint8_t* overlay,
                           uint8_t* color_mask, void* stream);
+
+/* The device part of the app's get_analysis (src/app/tools/analysis.py:133-250) for a pullback of N slices.  stack: f32 [N][H][W][stack_channels]
+ * (what octseg_mask_assemble writes; any value != 0 counts as set, as in octseg_render_results).  counts: int32 [N][stack_channels], the number of
+ * set pixels (np.nonzero, analysis.py:199-200; a class is present in a slice iff 0 < count < H * W, np.unique at analysis.py:189).
+ * radii: int32 [N][stack_channels][360], the ray walk of calculate_object_thickness (analysis.py:60-130) without trigonometry on the device:
+ *   ray_pix: device int32 [360][R], linear pixel index y * W + x of step r = 1 .. R of the ray at `angle` degrees, made by the host as
+ *            x = int(W / 2 + r * cos(radians(angle))), y = int(H / 2 + r * sin(radians(angle))) in CPython's double arithmetic (ids outside
+ *            [0, H * W) are clamped on the device: a wrong table gives wrong samples, never a stray read); may be null when R == 0;
+ *   ray_len: device int32 [360], the number of leading steps inside the frame (clamped to [0, R] on the device); later steps are never read.
+ * With v[r] = stack[n][ray_pix[angle][r - 1]][c] != 0 for r = 1 .. ray_len[angle]: f = the first r with v[r] set -- none: radius 0 (the
+ * reference's radii are >= 1, so 0 means "no object on this ray"); g = the first r > f with v[r] clear: radius g - 1 -- none: radius
+ * ray_len[angle].  A gap before the object is skipped, the first gap after it ends the ray, leaving the frame ends it found or not; the
+ * walk starts at step 1 (the centre is sampled only where truncation brings a later step back to it).  Integer results: they EQUAL the reference's, no tolerance.  The host mirror
+ * (oct_segmentation_amd/analysis.py) makes the table and turns counts and radii into the app's dict.
+ * Enqueue only (one clear of counts, two launches).  Null pointer: OCTSEG_BAD_ARG; N, H, W, stack_channels <= 0, stack_channels > 16, R < 0 or
+ * H * W >= 2^31: OCTSEG_BAD_SHAPE. */
+int octseg_stack_measure(const float* stack, int N, int H, int W, int stack_channels, const int* ray_pix, const int* ray_len, int R, int* counts,
+                         int* radii, void* stream);
 
 /* Criterion evaluated by octseg_dice_forward / octseg_net_train_step and differentiated by the backward entry points.
  * OCTSEG_LOSS_DICE (default) = smp.losses.DiceLoss(MULTILABEL_MODE, from_logits=True), the reference's (model.py:55);

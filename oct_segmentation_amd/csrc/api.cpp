@@ -268,6 +268,18 @@ int octseg_render_results(const float* stack, const uint8_t* frames, int N, int 
   return OCTSEG_OK;
 }
 
+// The measurements of the app's get_analysis (app/tools/analysis.py:60-130,189,199-200): see measure.hip.  Enqueue only.
+int octseg_stack_measure(const float* stack, int N, int H, int W, int stack_channels, const int* ray_pix, const int* ray_len, int R, int* counts,
+                         int* radii, void* stream) {
+  if (!stack || !ray_len || !counts || !radii || (!ray_pix && R != 0)) return fail(OCTSEG_BAD_ARG, "null argument");
+  if (N <= 0 || H <= 0 || W <= 0 || stack_channels <= 0 || stack_channels > 16)
+    return fail(OCTSEG_BAD_SHAPE, "stack_measure: empty batch or frame, or not 1..16 channels");
+  if (R < 0) return fail(OCTSEG_BAD_SHAPE, "stack_measure: negative ray table length");
+  if ((long long)H * W >= (1ll << 31)) return fail(OCTSEG_BAD_SHAPE, "stack_measure: H * W must be below 2^31");
+  HIPCHK(launch_stack_measure(stack, N, H, W, stack_channels, ray_pix, ray_len, R, counts, radii, (hipStream_t)stream));
+  return OCTSEG_OK;
+}
+
 int octseg_dice_forward(octseg_plan* p, void* workspace, const float* logits, const float* target, float* loss,
                         long long* stats, void* stream) {
   if (!p || !workspace || !logits || !target || !loss) return fail(OCTSEG_BAD_ARG, "null argument");

@@ -311,6 +311,11 @@ hipError_t launch_render_results(const float* stack, const uint8_t* frames, int 
                                  const uint8_t* class_rgb, int C, const uint8_t* alpha_tab, int ring_alpha, int iters, uint8_t* overlay,
                                  uint8_t* cmask, hipStream_t st);
 
+// the app's per-pullback measurements (measure.hip): set pixels per slice and channel, and calculate_object_thickness's ray walk per slice,
+// channel and degree from the host's pixel table; clears counts, then two launches
+hipError_t launch_stack_measure(const float* stack, int N, int H, int W, int SC, const int* ray_pix, const int* ray_len, int R, int* counts,
+                                int* radii, hipStream_t st);
+
 // fused optimizers over the flat fp32 arenas
 struct OptArgs {
   float* p; const float* g; float* m; float* v; size_t n;

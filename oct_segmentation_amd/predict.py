@@ -247,7 +247,9 @@ def main(argv=None):
     """src/predict.py:109-149 from ``configs/predict.yaml`` (``key=value`` overrides as with hydra): data_processing -> segment -> save_results,
     two PNGs per frame in ``save_dir``.  The frames go up once as uint8, the masks stay on the device from the nets to the rendering kernel
     (``segment_stack`` -> ``postprocess.save_results``); what comes back is the uint8 overlay and colour mask, 6 bytes per pixel instead of the
-    16 of the float32 stack.  Extra keys: ``compute_dtype`` (bf16 | fp16 | fp32), ``batch_size``, ``use_graph``, ``close_iterations``."""
+    16 of the float32 stack.  Extra keys: ``compute_dtype`` (bf16 | fp16 | fp32), ``batch_size``, ``use_graph``, ``close_iterations``, and
+    ``analysis`` (default false): also write ``{save_dir}/analysis.json``, the dict of the app's ``get_analysis`` measured on the same stack
+    (``analysis.analyze_stack``), with the frames as the slices of one pullback in sorted file-name order, as the app sorts its mask files."""
     import logging
     import sys
     import time
@@ -276,6 +278,12 @@ def main(argv=None):
     torch.cuda.synchronize()
     log.info(f'Prediction time: {time.time() - start_inference:.1f} s')
     save_results(images, stack, names, cfg['classes'], str(cfg['save_dir']), close_iterations=int(cfg.get('close_iterations', 1)))
+    if bool(cfg.get('analysis', False)):
+        from .analysis import analyze_stack
+        order = sorted(range(len(paths)), key=lambda i: os.path.basename(paths[i]))      # _image_paths is the glob's order
+        data = analyze_stack(stack[torch.tensor(order, device=stack.device)], [names[i] for i in order])
+        with open(os.path.join(str(cfg['save_dir']), 'analysis.json'), 'w') as f:
+            json.dump(data, f)
     log.info(f'Overall computation time: {time.time() - start:.1f} s')
     log.info('Complete')
     return 0
