@@ -35,7 +35,7 @@ constexpr int P3_RW = 18, P3_NPIX = 18 * 18, P3_PSTEP = P3_NTHREADS / (P3_RB / 1
 constexpr int P3_ABYTES = P3_NPASS * P3_PSTEP * P3_PITCH;
 constexpr int P3_OPITCH = P3_BN * 2 + 16;
 static_assert(P3_NPASS <= 8, "one window pass per tap");
-// grouped A-row map (conv_mfma.hip RowMap<true>): the 16 lanes of one ds_read_b128 LDS cycle read 16 consecutive pixels of a row
+// grouped A-row map (conv_mfma.hip RowMap): the 16 lanes of one ds_read_b128 LDS cycle read 16 consecutive pixels of a row
 __device__ __forceinline__ int p3_ty(int rr) { return (0xF00F0FF0u >> rr) & 1; }
 __device__ __forceinline__ int p3_tx(int rr) {
   const unsigned grp = ((0xF00F0FF0u >> rr) & 1) ? 0xF00F0FF0u : ~0xF00F0FF0u;
@@ -640,8 +640,7 @@ static P3Geom p3_geom(const ConvArgs& a) {
 }  // namespace
 
 bool conv3x3p_eligible(const ConvArgs& a, int dtype) {
-  static const bool on = getenv("OCTSEG_NO_CONV3X3P") == nullptr;   // A/B switch
-  if (!on || dtype == DT_F32) return false;
+  if (dtype == DT_F32) return false;
   if (a.ntaps != 9 || a.istride != 1 || a.ostride != 1 || a.ooy != 0 || a.oox != 0 || a.out_mode == OUT_HEAD_NCHW) return false;
   if (a.span_x != 3 || a.span_y != 3 || a.OH % P3_TH != 0 || a.OW % TW != 0 || a.IH != a.OH || a.IW != a.OW) return false;
   // the 128-channel N tile with 64-channel K chunks; K >= 128: measured on one box against conv_mfma_kernel (U-Net++/resnet101 16 x 704^2,
@@ -675,12 +674,9 @@ static hipError_t p3_launch_k(const ConvArgs& a, const P3Geom& g, hipStream_t st
 }
 template <typename T>
 static hipError_t p3_launch(const ConvArgs& a, const P3Geom& g, hipStream_t st) {
-  static const bool plain = getenv("OCTSEG_P3_PLAIN") != nullptr;   // A/B switch: the head-of-tap variant
-  static const bool keep_aff = getenv("OCTSEG_P3_AFF") != nullptr;  // A/B switch: identity affine also where no source needs one
   if constexpr (std::is_same<T, f16_t>::value) return p3_launch_k<T, false>(a, g, st);   // (the interleaved variant's f16 instantiation spills)
   else {
-    if (plain) return p3_launch_k<T, false>(a, g, st);
-    bool noaff = !keep_aff;
+    bool noaff = true;   // no source needs the lazy affine: the variant without it
     for (int i = 0; i < a.nsrc; ++i) noaff = noaff && a.src[i].scale == nullptr && a.src[i].shift == nullptr && a.src[i].relu == 0;
     return noaff ? p3_launch_k<T, true, true>(a, g, st) : p3_launch_k<T, true, false>(a, g, st);
   }

@@ -77,16 +77,8 @@ template <> struct Tr<bf16_t> {
     typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
     typedef __attribute__((ext_vector_type(2))) short s16x2_t;
     f32x2_t x = {__uint_as_float(w << 16), __uint_as_float(w & 0xffff0000u)};
-#ifdef OCTSEG_SCALAR_AFFINE
-    // Two v_fma_f32 instead of one v_pk_fma_f32: beside MFMAs a packed-f32 VALU instruction costs ~22 cycles more than the two scalar
-    // ones it replaces (MI355X_MICROARCH.md, 'price of one filler beside MFMAs').  asm so that -O3's SLP pass cannot re-pack them.
-    // A translation unit whose staging runs in MFMA gaps defines OCTSEG_SCALAR_AFFINE before including this header.
-    asm("v_fma_f32 %0, %1, %2, %3" : "=v"(x[0]) : "v"(x[0]), "v"(s0), "v"(t0));
-    asm("v_fma_f32 %0, %1, %2, %3" : "=v"(x[1]) : "v"(x[1]), "v"(s1), "v"(t1));
-#else
     const f32x2_t s2 = {s0, s1}, t2 = {t0, t1};
     x = __builtin_elementwise_fma(x, s2, t2);
-#endif
     const bf16x2_t b = __builtin_convertvector(x, bf16x2_t);
     const s16x2_t m = __builtin_elementwise_max(__builtin_bit_cast(s16x2_t, b), __builtin_bit_cast(s16x2_t, floor16));
     return __builtin_bit_cast(unsigned, m);

@@ -36,16 +36,10 @@ namespace octseg {
 #define STAMP(var) do { } while (0)
 #endif
 
-// A-row (0..31 of a 32x32 MFMA tile) -> pixel inside the wave's 2x16-pixel strip.  Plain: two rows of 16.
-// Grouped: the 16 lanes that one ds_read_b128 LDS cycle serves ({0-3,12-15,20-27} / {4-11,16-19,28-31},
-// MI355X_MICROARCH.md LDS table) read 16 CONSECUTIVE pixels of one row, which the pitch-128 XOR-swizzled
-// window serves without bank conflicts for every tap shift.
-template <bool GROUPED> struct RowMap;
-template <> struct RowMap<false> {
-  static __device__ __forceinline__ int ty(int rr) { return rr >> 4; }
-  static __device__ __forceinline__ int tx(int rr) { return rr & 15; }
-};
-template <> struct RowMap<true> {
+// A-row (0..31 of a 32x32 MFMA tile) -> pixel inside the wave's 2x16-pixel strip, grouped: the 16 lanes that one ds_read_b128 LDS
+// cycle serves ({0-3,12-15,20-27} / {4-11,16-19,28-31}, MI355X_MICROARCH.md LDS table) read 16 CONSECUTIVE pixels of one row, which
+// the pitch-128 XOR-swizzled window serves without bank conflicts for every tap shift.
+struct RowMap {
   static constexpr unsigned MASK_B = 0xF00F0FF0u;
   static __device__ __forceinline__ int ty(int rr) { return (MASK_B >> rr) & 1; }
   static __device__ __forceinline__ int tx(int rr) {
@@ -53,12 +47,6 @@ template <> struct RowMap<true> {
     return __popc(grp & ((1u << rr) - 1u));
   }
 };
-
-#ifdef OCTSEG_PLAIN_ROWMAP
-constexpr bool ROWMAP_GROUPED = false;   // A/B build switch
-#else
-constexpr bool ROWMAP_GROUPED = true;
-#endif
 
 // M sub-tiles (2 rows x 16 pixels each) per wave: 2, or 4 in the wide-N configuration (NT = 4, 64-byte K chunks: four waves of
 // 128 pixels x 128 channels, one per SIMD with the whole register file -- 256 accumulators)
@@ -110,7 +98,7 @@ template <typename T> __host__ __device__ constexpr bool conv_m16(int mt) { retu
 
 // Epilogue shared by the conv kernels: bias, BN partials, LDS transpose, 16-byte stores / accumulates.
 // All waves must be past their last LDS read of the main loop (barrier) when this is entered.
-template <typename T, int NT, int WN, int WM, bool GROUPED, int MT, bool T11 = false>
+template <typename T, int NT, int WN, int WM, int MT, bool T11 = false>
 static __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, char* smem, f32x16_t (&acc)[conv_m16<T>(MT) ? 1 : MT][conv_m16<T>(MT) ? 1 : NT],
                                                      f32x4_t (&acc16)[conv_m16<T>(MT) ? 2 * MT : 1][conv_m16<T>(MT) ? 2 * NT : 1], const TilePos& tp) {
   // 2-byte types accumulate in 16 x 16 blocks (v_mfma_f32_16x16x32: block row mb = tile row wm * 2 * MT + mb, element j of lane (r16, g) =
@@ -141,12 +129,11 @@ static __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, char* sm
     // search and the per-vector 64-bit address math (the general path is ~4000 instructions per thread).
     if (!head && (T11 || (y0 + TH <= a.OH && x0 + TW <= a.OW))) {   // (11 x 11 tiles divide their maps: always whole)
       constexpr int ES = (int)sizeof(T);
-      // accumulator element i of lane (r, h) is A row rr = (i & 3) + 8 * (i >> 2) + 4 * h; its pixel inside the wave's strip:
-      //   plain row map:   row (i >> 3), column (i & 3) + 8 * ((i >> 2) & 1) + 4 * h
-      //   grouped row map: row h ^ [(i >> 2) is 1 or 2], column 4 * (i >> 2) + (i & 3)      (RowMap<true>)
+      // accumulator element i of lane (r, h) is A row rr = (i & 3) + 8 * (i >> 2) + 4 * h; its pixel inside the wave's strip (RowMap):
+      // row h ^ [(i >> 2) is 1 or 2], column 4 * (i >> 2) + (i & 3)
       const int lchan = (wn * NT * 32 + r) * ES;
-      const int lbase = GROUPED ? (wm * 2 * MT * TW + h * TW) * OPITCH + lchan : (wm * 2 * MT * TW + 4 * h) * OPITCH + lchan;
-      const int lbase_x = (wm * 2 * MT * TW + (1 - h) * TW) * OPITCH + lchan;   // grouped: the other row of the strip
+      const int lbase = (wm * 2 * MT * TW + h * TW) * OPITCH + lchan;
+      const int lbase_x = (wm * 2 * MT * TW + (1 - h) * TW) * OPITCH + lchan;   // the other row of the strip
       (void)lbase_x;
       // transposed tile into LDS; the bias add and the BN partial sums only where the layer has them (uniform
       // branches: a dgrad has neither and saves three of its four vector instructions per element)
@@ -189,14 +176,8 @@ static __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, char* sm
               if constexpr (HAS_BIAS) val += bias;
               if constexpr (HAS_RELU) val = clamp_lo(val, 0.f);   // eval, BatchNorm folded: the activation is stored, not the raw conv output
               if constexpr (HAS_STAT) { s1[nt] += val; s2[nt] += val * val; }
-              int off, lb;
-              if constexpr (GROUPED) {
-                off = (mt * 2 * TW + 4 * (i >> 2) + (i & 3)) * OPITCH + nt * 32 * ES;
-                lb = ((0x6 >> (i >> 2)) & 1) ? lbase_x : lbase;
-              } else {
-                off = ((mt * 2 + (i >> 3)) * TW + (i & 3) + 8 * ((i >> 2) & 1)) * OPITCH + nt * 32 * ES;
-                lb = lbase;
-              }
+              const int off = (mt * 2 * TW + 4 * (i >> 2) + (i & 3)) * OPITCH + nt * 32 * ES;
+              const int lb = ((0x6 >> (i >> 2)) & 1) ? lbase_x : lbase;
               if (sizeof(T) == 4) *(float*)(otile + lb + off) = val;
               else *(unsigned short*)(otile + lb + off) = Tr<T>::bits16(val);
             }
@@ -394,7 +375,7 @@ static __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, char* sm
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         const int rr = (i & 3) + 8 * (i >> 2) + 4 * h;   // A row of this accumulator element
-        const int ty = wm * 2 * MT + mt * 2 + RowMap<GROUPED>::ty(rr), tx = RowMap<GROUPED>::tx(rr);
+        const int ty = wm * 2 * MT + mt * 2 + RowMap::ty(rr), tx = RowMap::tx(rr);
         const int gy = y0 + ty, gx = x0 + tx;
         float val = acc[mt][nt][i] + bias;
         if (a.relu_out) val = clamp_lo(val, 0.f);
@@ -626,7 +607,7 @@ __global__ __launch_bounds__(64 * WM * WN, ((WM * WN == 4 && wave_mt(NT, RB) == 
     // 144-byte pitch spreads them over all 16 sixteen-byte slots of the 256-byte LDS line for every tap shift and window
     // width (the plain map mixed lanes of both strip rows in one group: two 2-way conflicts per group at RW = 18, 30 % of
     // all LDS cycles of the 3x3 layers, profiles/r1_sq_counters_conv3x3_512_256_352.txt)
-    const int ty = wm * 2 * MT + mt * 2 + RowMap<ROWMAP_GROUPED>::ty(r), tx = RowMap<ROWMAP_GROUPED>::tx(r);
+    const int ty = wm * 2 * MT + mt * 2 + RowMap::ty(r), tx = RowMap::tx(r);
     abase[mt] = ((ty * lstride) * RW + tx * lstride) * PITCH + h * 16;
   }
   int bswz[NT];  // XOR swizzle of the 16-byte chunk index inside a slab row (matches pack_weight_image)
@@ -1352,7 +1333,7 @@ __global__ __launch_bounds__(64 * WM * WN, ((WM * WN == 4 && wave_mt(NT, RB) == 
 #ifdef OCTSEG_STAMP
   STAMP(k2);
 #endif
-  conv_epilogue<T, NT, WN, WM, ROWMAP_GROUPED, MT, T11>(a, smem, acc, acc16, tp);
+  conv_epilogue<T, NT, WN, WM, MT, T11>(a, smem, acc, acc16, tp);
 #ifdef OCTSEG_STAMP
   STAMP(k3);
   if (a.stamp != nullptr && lane == 0) {
@@ -1433,48 +1414,49 @@ struct Choice { Variant v; int dbuf; size_t lds; int resident; int ring3; int ri
 // <= 1024: 56.38, <= 2304: 56.09, <= 4608: 55.5, no limit 55.68).  `pool_ok` =
 // false: the geometry alone (a pooled destination needs even tiles -- such a launch keeps the 16-pixel tiling but must keep the same weight image)
 static bool tile11_geom(const ConvArgs& a, int esz) {
-  static const bool off = getenv("OCTSEG_NO_TILE11") != nullptr;   // A/B switch
-  if (off || esz != 2 || a.taps_per_src > 0) return false;
+  if (esz != 2 || a.taps_per_src > 0) return false;
   if (a.ntaps != 9 || a.span_x != 3 || a.span_y != 3 || a.istride != 1 || a.ostride != 1 || a.ooy != 0 || a.oox != 0) return false;
   if (a.out_mode == OUT_HEAD_NCHW || a.IH != a.OH || a.IW != a.OW || a.OH % 11 != 0 || a.OW % 11 != 0 || a.OH > 88 || a.OW > 88) return false;
   if (a.OH % 16 == 0 && a.OW % 16 == 0) return false;
   if (a.Cout <= 64 || a.Cin < 64) return false;
   const long long wg16 = (long long)a.N * ((a.OH + 15) / 16) * ((a.OW + 15) / 16) * ((a.Cout + 127) / 128);
-  static const long long maxwg = getenv("OCTSEG_TILE11_MAXWG") ? atoll(getenv("OCTSEG_TILE11_MAXWG")) : 4608;   // experiments
   // ... and only where the 11-pixel grid gives every CU a workgroup: on a grid that leaves CUs idle a layer takes as long as ONE workgroup, and this
   // loop restages its window between K chunks with nobody to overlap it (fp16 ensemble, one frame: 147 -> 130 frames/s without this bound)
   static const long long minwg = getenv("OCTSEG_TILE11_MINWG") ? atoll(getenv("OCTSEG_TILE11_MINWG")) : 256;
   const long long wg11 = (long long)a.N * (a.OH / 11) * (a.OW / 11) * ((a.Cout + 127) / 128);
-  return wg16 <= maxwg && wg11 >= minwg;
+  return wg16 <= 4608 && wg11 >= minwg;
+}
+
+// LDS of the 4-wave 128-channel tile with ONE window buffer (LOOP_T11 and the masked loop's single-buffer form): 6 passes of 32 pixels (a 13 x 13
+// window) + two slab slots against the epilogue's tile: 60 KB -> two workgroups per CU
+static size_t lds_single128(int esz) {
+  const size_t main_loop = (size_t)6 * 32 * 144 + 2 * (size_t)128 * 128;
+  const size_t epi = (size_t)128 * (128 * esz + 16) + (size_t)2 * 128 * 2 * sizeof(float);
+  return main_loop > epi ? main_loop : epi;
+}
+
+// a pooled destination needs even tiles: no 11-pixel tiling
+static bool any_pooled_dst(const ConvArgs& a) {
+  for (int i = 0; i < a.ndst; ++i)
+    if (a.dst[i].pool != 0) return true;
+  return false;
 }
 
 static Choice choose(const ConvArgs& a, int esz) {
   Choice c;
   c.ring3 = 0; c.ring1 = 0; c.tile11 = 0;
   const bool t11 = tile11_geom(a, esz);
-  if (t11) {
-    bool pool = false;
-    for (int i = 0; i < a.ndst; ++i) pool = pool || a.dst[i].pool != 0;
-    if (!pool) {   // 13 x 13 window = 6 passes of 32 pixels, two slab slots: 60 KB -> two workgroups per CU
-      c.v = Variant{2, 2, 2, 128}; c.dbuf = 0; c.resident = 0; c.tile11 = 1;
-      const size_t main_loop = (size_t)6 * 32 * 144 + 2 * (size_t)128 * 128;
-      const size_t epi = (size_t)128 * (128 * esz + 16) + (size_t)2 * 128 * 2 * sizeof(float);
-      c.lds = main_loop > epi ? main_loop : epi;
-      return c;
-    }
+  if (t11 && !any_pooled_dst(a)) {
+    c.v = Variant{2, 2, 2, 128}; c.dbuf = 0; c.resident = 0; c.tile11 = 1; c.lds = lds_single128(esz);
+    return c;
   }
-  {
-    // plain four-tap stride-1 launches (a ConvTranspose2d forward parity: 2 x 2 taps, output stride 2) with > 64 output channels: the masked loop's
-    // 4-wave tile with one window buffer and register prefetch (every chunk meets all four taps); OCTSEG_NO_RP4: the rolled loop (A/B switch)
-    static const bool no_rp4 = getenv("OCTSEG_NO_RP4") != nullptr;
-    if (!no_rp4 && esz == 2 && a.taps_per_src == 0 && a.ntaps == 4 && a.span_x == 2 && a.span_y == 2 && a.istride == 1 &&
-        a.out_mode != OUT_HEAD_NCHW && a.Cout > 64 && a.Cin >= 64) {
-      c.v = Variant{2, 2, 2, 128}; c.dbuf = 0; c.resident = 0; c.tile11 = 3;   // (3: the masked loop without per-source lists)
-      const size_t main_loop = (size_t)6 * 32 * 144 + 2 * (size_t)128 * 128;
-      const size_t epi = (size_t)128 * (128 * esz + 16) + (size_t)2 * 128 * 2 * sizeof(float);
-      c.lds = main_loop > epi ? main_loop : epi;
-      return c;
-    }
+  // plain four-tap stride-1 launches (a ConvTranspose2d forward parity: 2 x 2 taps, output stride 2) with > 64 output channels: the masked loop's
+  // 4-wave tile with one window buffer and register prefetch (every chunk meets all four taps)
+  if (esz == 2 && a.taps_per_src == 0 && a.ntaps == 4 && a.span_x == 2 && a.span_y == 2 && a.istride == 1 &&
+      a.out_mode != OUT_HEAD_NCHW && a.Cout > 64 && a.Cin >= 64) {
+    c.v = Variant{2, 2, 2, 128}; c.dbuf = 0; c.resident = 0; c.tile11 = 3;   // (3: the masked loop without per-source lists)
+    c.lds = lds_single128(esz);
+    return c;
   }
   if (a.taps_per_src > 0) {   // masked loop: the 128-channel N tile, 64-channel chunks (conv_masked_eligible checked the rest)
     // four taps per source: the 4-wave tile with one window buffer, two workgroups per CU -- on 11 x 11 pixels where the map is a multiple of 11
@@ -1482,12 +1464,8 @@ static Choice choose(const ConvArgs& a, int esz) {
     static const bool force_dbuf = getenv("OCTSEG_MASKED_DBUF") != nullptr;   // A/B switch
     if (!force_dbuf && a.taps_per_src == 4 && esz == 2 && a.ntaps == 9 && a.span_x == 3 && a.span_y == 3) {
       c.v = Variant{2, 2, 2, 128}; c.dbuf = 0; c.resident = 0;
-      bool pool = false;
-      for (int i = 0; i < a.ndst; ++i) pool = pool || a.dst[i].pool != 0;
-      c.tile11 = (!pool && a.OH % 11 == 0 && a.OW % 11 == 0 && !(a.OH % 16 == 0 && a.OW % 16 == 0) && a.OH <= 88 && a.OW <= 88) ? 1 : 0;
-      const size_t main_loop = (size_t)6 * 32 * 144 + 2 * (size_t)128 * 128;
-      const size_t epi = (size_t)128 * (128 * esz + 16) + (size_t)2 * 128 * 2 * sizeof(float);
-      c.lds = main_loop > epi ? main_loop : epi;
+      c.tile11 = (!any_pooled_dst(a) && a.OH % 11 == 0 && a.OW % 11 == 0 && !(a.OH % 16 == 0 && a.OW % 16 == 0) && a.OH <= 88 && a.OW <= 88) ? 1 : 0;
+      c.lds = lds_single128(esz);
       return c;
     }
     for (int wm = 4; wm >= 2; wm -= 2) {
@@ -1505,7 +1483,6 @@ static Choice choose(const ConvArgs& a, int esz) {
   // output channels -- half the activation loads, lazy-BN arithmetic and LDS stores per MFMA, the input read once instead of
   // once per N tile -- and a wave reads 8 fragments per 16 MFMAs instead of 4 per 4.  LDS: 2 x 30 KiB windows + 3 x 16 KiB slabs.
   {
-    static const bool off = getenv("OCTSEG_NO_N256") != nullptr;   // A/B switch
     const int n256 = (a.Cout + 255) / 256;
     const int kc = 64 / esz;
     // Measured per layer (U-Net++/resnet101, 16 x 704^2, profiles/r2_layers_alone.csv): 1024 -> 256 @176^2 forward 2252 -> 2072 us
@@ -1514,11 +1491,9 @@ static Choice choose(const ConvArgs& a, int esz) {
     // 88^2 grids lose a round.  So: exactly 256 output channels, K >= 256, a grid of >= 1024 workgroups.
     // ... and not where the persistent kernel takes the layer with the 128-channel tile (16-divisible maps, 2-byte types): on
     // v_mfma_f32_16x16x32 it beats this 32x32x16 tile (same box: decoder forward 14.0 -> 13.6 ms, data gradients 15.5 -> 15.4)
-    static const bool no_p3 = getenv("OCTSEG_NO_CONV3X3P") != nullptr || getenv("OCTSEG_KEEP_N256") != nullptr;   // A/B switches
-    const bool p3 = !no_p3 && esz == 2 && a.ostride == 1 && a.OH % 16 == 0 && a.OW % 16 == 0 && a.IH == a.OH && a.IW == a.OW;
+    const bool p3 = esz == 2 && a.ostride == 1 && a.OH % 16 == 0 && a.OW % 16 == 0 && a.IH == a.OH && a.IW == a.OW;
     const bool fits = !p3 && a.Cout == 256 && a.Cin >= 256 && (long long)a.N * ((a.OH + 15) / 16) * ((a.OW + TW - 1) / TW) >= 1024;
-    static const bool all = getenv("OCTSEG_N256_ALL") != nullptr;   // experiments: every >= 256-channel 3x3 layer
-    if (!off && !t11 && (fits || all) && a.ntaps == 9 && a.istride == 1 && a.Cout > 128 && (n256 * 256 - a.Cout) * 10 <= a.Cout && a.Cin > kc) {
+    if (!t11 && fits && a.ntaps == 9 && a.istride == 1 && a.Cout > 128 && (n256 * 256 - a.Cout) * 10 <= a.Cout && a.Cin > kc) {
       const Variant v{4, 2, 2, 64};   // 2 x 2 waves of (4 M sub-tiles x 4 N sub-tiles)
       int npass = 0;
       const size_t lds = variant_lds(a, v, esz, 1, &npass);
@@ -1536,9 +1511,8 @@ static Choice choose(const ConvArgs& a, int esz) {
     // K-thin layers (one K chunk: the data gradients of the 64-channel decoder layers) whose 128-channel tiling leaves a quarter or more of
     // its last N tile empty take 64-channel N tiles: 192 <- 64 @352^2 (the skip half of x_1_3.conv1's tied data gradient) 1.090 -> 0.925 ms.
     // With several K chunks the lost A reuse costs more than the empty half tile (192 <- 256 @176^2: 0.677 -> 0.727 ms).
-    static const bool off = getenv("OCTSEG_NO_BN64_THIN") != nullptr;   // A/B switch
     const int t128 = (a.Cout + 127) / 128;
-    if (!off && a.Cout > 64 && a.ntaps == 9 && a.Cin <= 128 / esz && a.Cout % 64 == 0 && (t128 * 128 - a.Cout) * 4 >= t128 * 128) { NT = 1; WN = 2; }
+    if (a.Cout > 64 && a.ntaps == 9 && a.Cin <= 128 / esz && a.Cout % 64 == 0 && (t128 * 128 - a.Cout) * 4 >= t128 * 128) { NT = 1; WN = 2; }
   }
   // Small grids (small per-GPU batches -- strong scaling -- and the deepest stages): a multi-tap layer whose 16x16-pixel x 128-channel
   // tiles number fewer than half the CUs runs at the speed of ONE workgroup's loop (U-Net++/resnet101 at 2 frames per GPU: x_0_0.conv1,
@@ -1546,10 +1520,9 @@ static Choice choose(const ConvArgs& a, int esz) {
   // quadruple the workgroup count at the price of slab reuse, which an under-filled chip does not miss.
   bool small_grid = false;
   {
-    static const bool off = getenv("OCTSEG_NO_SMALLGRID") != nullptr;   // A/B switch
     const int bn = NT * 32 * WN;
     const long long w16 = (long long)a.N * ((a.OH + 15) / 16) * ((a.OW + TW - 1) / TW) * ((a.Cout + bn - 1) / bn);
-    small_grid = !off && a.ntaps > 1 && w16 < 128;
+    small_grid = a.ntaps > 1 && w16 < 128;
     if (small_grid && a.Cout > 64) { NT = 1; WN = 2; }
   }
   const int kc128 = 128 / esz;
@@ -1584,8 +1557,6 @@ static Choice choose(const ConvArgs& a, int esz) {
     }
   }
   if (small_grid) wm_first = 2;
-  static const int force_wm = getenv("OCTSEG_FORCE_WM") ? atoi(getenv("OCTSEG_FORCE_WM")) : 0;   // A/B switch
-  if (force_wm) wm_first = force_wm;
   const int order[2] = {wm_first, wm_first == 4 ? 2 : 4};
   const int nchunks_c = (a.Cin + RB / esz - 1) / (RB / esz);
   // a single K chunk never restages its window: a second buffer would only cost occupancy
@@ -1602,8 +1573,7 @@ static Choice choose(const ConvArgs& a, int esz) {
         {
           const size_t slab = (size_t)v.NT * 32 * v.WN * v.RB;
           const int nd = (int)(slab / 1024), nw = v.WM * v.WN;
-          static const bool no_ring3 = getenv("OCTSEG_NO_RING3") != nullptr || getenv("OCTSEG_NO_RUN9") != nullptr;   // A/B switches
-          if (!no_ring3 && pref_dbuf && a.ntaps == 9 && npass <= 8 && nd % nw == 0 && lds + slab <= cap) { c.ring3 = 1; c.lds = lds + slab; }
+          if (pref_dbuf && a.ntaps == 9 && npass <= 8 && nd % nw == 0 && lds + slab <= cap) { c.ring3 = 1; c.lds = lds + slab; }
         }
         // thin layers: one K chunk and slabs small enough to keep all taps in LDS -> no per-tap DMA wait / barrier
         const size_t slab = (size_t)v.NT * 32 * v.WN * v.RB;
@@ -1614,8 +1584,7 @@ static Choice choose(const ConvArgs& a, int esz) {
         // one K chunk, 3x3, slabs too big to stay resident: slab ring with counted waits (run9s)
         {
           const int nd = (int)(slab / 1024), nw = v.WM * v.WN;
-          static const bool no_run9s = getenv("OCTSEG_NO_RUN9S") != nullptr || getenv("OCTSEG_NO_RUN9") != nullptr;   // A/B switches
-          if (!no_run9s && !c.resident && !pref_dbuf && nchunks_c == 1 && a.ntaps == 9 && v.RB == 128 && nd % nw == 0 && lds + slab <= cap) {
+          if (!c.resident && !pref_dbuf && nchunks_c == 1 && a.ntaps == 9 && v.RB == 128 && nd % nw == 0 && lds + slab <= cap) {
             c.ring1 = 1; c.lds = lds + slab;
           }
         }
@@ -1637,8 +1606,6 @@ hipError_t dispatch(const ConvArgs& a_in, hipStream_t st) {
     a.src_uniform = 1;
     for (int i = 1; i < a.nsrc; ++i)
       if (a.src[i].c0 % KC != 0) a.src_uniform = 0;
-    static const bool no_usrc = getenv("OCTSEG_NO_UNIFORM_SRC") != nullptr;   // A/B switch
-    if (no_usrc) a.src_uniform = 0;
   }
   const int loop = a.taps_per_src > 0 ? (c.tile11 ? LOOP_MASKED_T11 : LOOP_MASKED) : c.tile11 == 3 ? LOOP_MASKED : c.tile11 ? LOOP_T11
                    : c.resident ? LOOP_RESIDENT : (c.ring3 ? LOOP_RUN9 : (c.ring1 ? LOOP_RUN9S : ((a.ntaps == 1 && c.dbuf) ? LOOP_1X1 : LOOP_GENERIC)));
@@ -1700,10 +1667,24 @@ static bool flatten_1x1(ConvArgs& a) {
   return true;
 }
 
+// Which kernel runs a conv launch: decided HERE, once, for launch_conv and for conv_num_mtiles_flat (the BatchNorm statistics slab that the chosen
+// kernel writes has one row per M tile / workgroup of THAT kernel).  A launch with per-source tap subsets belongs to conv_mfma's masked loop.
+enum ConvRoute { ROUTE_THIN, ROUTE_GEMM1X1, ROUTE_CONV3X3P, ROUTE_MFMA };
+static ConvRoute conv_route(const ConvArgs& a, int dtype) {
+  if (a.taps_per_src > 0) return ROUTE_MFMA;
+  if (thin_conv_eligible(a, dtype)) return ROUTE_THIN;
+  if (gemm1x1_eligible(a, dtype)) return ROUTE_GEMM1X1;
+  if (conv3x3p_eligible(a, dtype)) return ROUTE_CONV3X3P;
+  return ROUTE_MFMA;
+}
+
 int conv_num_mtiles_flat(const ConvArgs& a0, int dtype) {
-  if (thin_conv_eligible(a0, dtype)) return thin_conv_rows(a0);
-  if (gemm1x1_eligible(a0, dtype)) return gemm1x1_rows(a0);
-  if (conv3x3p_eligible(a0, dtype)) return conv3x3p_rows(a0);
+  switch (conv_route(a0, dtype)) {
+    case ROUTE_THIN: return thin_conv_rows(a0);
+    case ROUTE_GEMM1X1: return gemm1x1_rows(a0);
+    case ROUTE_CONV3X3P: return conv3x3p_rows(a0);
+    case ROUTE_MFMA: break;
+  }
   ConvArgs a = a0;
   flatten_1x1(a);
   return conv_num_mtiles(a, dtype);
@@ -1711,8 +1692,7 @@ int conv_num_mtiles_flat(const ConvArgs& a0, int dtype) {
 
 // what the masked loop needs of a launch with per-source tap subsets (the plan falls back to its other form when this says no)
 bool conv_masked_eligible(const ConvArgs& a, int dtype) {
-  static const bool off = getenv("OCTSEG_NO_MASKED_LOOP") != nullptr;   // A/B switch
-  if (off || dtype == DT_F32 || a.taps_per_src <= 0 || a.taps_per_src > 8 || a.ntaps < 2 || a.ntaps > 16) return false;
+  if (dtype == DT_F32 || a.taps_per_src <= 0 || a.taps_per_src > 8 || a.ntaps < 2 || a.ntaps > 16) return false;
   if (a.istride != 1 || a.ostride != 1 || a.out_mode == OUT_HEAD_NCHW || a.Cout <= 64 || a.Cout % 8 != 0) return false;
   const int KC = 64;
   for (int i = 0; i < a.nsrc; ++i)
@@ -1724,15 +1704,18 @@ bool conv_masked_eligible(const ConvArgs& a, int dtype) {
 
 hipError_t launch_conv(int dtype, const ConvArgs& a0, hipStream_t st) {
   if (a0.ntaps <= 0) return hipSuccess;
+  switch (conv_route(a0, dtype)) {
+    case ROUTE_THIN: return launch_thin_conv(dtype, a0, st);
+    case ROUTE_GEMM1X1: return launch_gemm1x1(dtype, a0, st);
+    case ROUTE_CONV3X3P: return launch_conv3x3p(dtype, a0, st);
+    case ROUTE_MFMA: break;
+  }
   if (a0.taps_per_src > 0) {
     if (!conv_masked_eligible(a0, dtype)) return hipErrorInvalidValue;
     ConvArgs a = a0;
     a.tile_order = 1;
     return dtype == DT_F16 ? dispatch<f16_t>(a, st) : dispatch<bf16_t>(a, st);
   }
-  if (thin_conv_eligible(a0, dtype)) return launch_thin_conv(dtype, a0, st);
-  if (gemm1x1_eligible(a0, dtype)) return launch_gemm1x1(dtype, a0, st);
-  if (conv3x3p_eligible(a0, dtype)) return launch_conv3x3p(dtype, a0, st);
   ConvArgs a = a0;
   flatten_1x1(a);
   {

@@ -87,8 +87,6 @@ __device__ __forceinline__ bool slab_sum(const float* __restrict__ slab, int row
 // channels per block of the finalize grid: few rows -> 32 (one 256-byte segment per row), long slabs -> down to 4 (a 32-byte sector per
 // row; the slab was just written and sits in L2), so that a thread walks at most a few dozen rows
 static inline int slab_cpb(int rows) {
-  static const int force = getenv("OCTSEG_SLAB_CPB") ? atoi(getenv("OCTSEG_SLAB_CPB")) : 0;   // A/B switch
-  if (force == 4 || force == 8 || force == 16 || force == 32) return force;
   return rows <= 512 ? 32 : rows <= 2048 ? 16 : rows <= 6144 ? 8 : 4;
 }
 // row groups: only where a thread would still walk more than 256 rows (slabs beyond 64 k rows at 4 channels per block), within the scratch
@@ -307,18 +305,10 @@ hipError_t launch_bn_act(int dtype, const BnActArgs& a, hipStream_t st) {
 
 // ------------------------------------------------------------------ BN backward
 // dz = g * mask;  slab[row][c] = (sum dz, sum dz * xhat),  xhat = (y - mean) * rstd
-// FUSED: the kernel also finishes the reduction (what bn_bwd_finalize_kernel did in a launch of its own, 126 per step): rows are
-// grouped by 32; the workgroup whose ticket completes a group sums that group's rows in row order (double) into a partial, the one
-// whose ticket completes the last group sums the <= 32 partials in group order and writes dgamma / dbeta / coef -- a fixed summation
-// order, so still deterministic.  Hand-off (cdna_hip_programming.md Guideline 16 / split-K recipe): slab rows and partials are stored
-// write-through (sc1: agent-scope relaxed atomic stores), every storing wave drains vmcnt, workgroup barrier, ONE lane takes the ticket
-// (relaxed agent fetch_add); the finisher does one agent acquire (+ vmcnt drain + barrier) and then reads with plain loads, all in flight
-// at once (sc1 / atomic loads were issued one by one: 64 dependent round trips per launch cost 60 us, measured).
-template <typename T, bool FUSED>
+template <typename T>
 __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const BnBwdArgs a) {
   constexpr int VEC = EV<T>::VEC;
   __shared__ float red[256][VEC * 2 + 1];
-  __shared__ unsigned s_last;
   const int vpc = a.C / VEC;                     // vectors per pixel (power of two)
   const int tpv = vpc >= 256 ? 1 : 256 / vpc;    // threads sharing one channel vector
   const int cv = (vpc >= 256 ? blockIdx.y * 256 : 0) + (threadIdx.x % (vpc >= 256 ? 256 : vpc));
@@ -361,96 +351,17 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const BnBwdArgs a) {
 #pragma unroll
       for (int i = 0; i < VEC; ++i) { s1[i] += red[threadIdx.x + k * vpc][i]; s2[i] += red[threadIdx.x + k * vpc][VEC + i]; }
     float* o = a.slab + ((size_t)blockIdx.x * a.C + c) * 2;
-    if constexpr (FUSED) {
 #pragma unroll
-      for (int i = 0; i < VEC; ++i) {   // one 8-byte write-through store per channel: (sum dz, sum dz * xhat)
-        const unsigned long long bits = (unsigned long long)__float_as_uint(s1[i]) | ((unsigned long long)__float_as_uint(s2[i]) << 32);
-        __hip_atomic_store((unsigned long long*)(o + 2 * i), bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < VEC; ++i) { o[2 * i] = s1[i]; o[2 * i + 1] = s2[i]; }
-    }
+    for (int i = 0; i < VEC; ++i) { o[2 * i] = s1[i]; o[2 * i + 1] = s2[i]; }
   }
-  if constexpr (FUSED) {
-    const int rows = gridDim.x, G = (rows + 31) / 32, grp = blockIdx.x / 32;
-    const int r0 = grp * 32, r1 = min(rows, r0 + 32);
-    const int cb0 = (vpc >= 256 ? blockIdx.y * 256 : 0) * VEC;            // first channel of this block column
-    const int nval = (vpc >= 256 ? 256 : vpc) * VEC * 2;                    // (sum, sum) pairs of its channels, as floats
-    unsigned* cg = a.fcnt + blockIdx.y * 33 * 32;                           // tickets of this column: group g at [g * 32] (a 128-byte line each: atomics on
-                                                                            // one line serialise at ~12 ns), the top ticket at [32 * 32]
-    double* fp = a.fpart + (size_t)blockIdx.y * 32 * (256 * VEC * 2);       // [group][nval] partials of this column
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                        // every storing wave: its row is out
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const unsigned old = __hip_atomic_fetch_add(&cg[grp * 32], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      s_last = old == (unsigned)(r1 - r0 - 1) ? 1u : 0u;
-      if (s_last) {
-        cg[grp * 32] = 0u;                                                  // ready for the next launch (kernel boundary publishes it)
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
-    }
-    __syncthreads();
-    if (!s_last) return;
-    // (plain loads behind the acquire: 32 independent loads per value in flight, summed in row order)
-    for (int i = threadIdx.x; i < nval; i += 256) {
-      const float* col = a.slab + ((size_t)r0 * a.C + cb0) * 2 + i;
-      float v[32];
-#pragma unroll
-      for (int k = 0; k < 32; ++k) v[k] = col[(size_t)min(k, r1 - r0 - 1) * a.C * 2];
-      double s = 0.0;
-#pragma unroll
-      for (int k = 0; k < 32; ++k) s += k < r1 - r0 ? (double)v[k] : 0.0;
-      __hip_atomic_store(fp + (size_t)grp * nval + i, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const unsigned old = __hip_atomic_fetch_add(&cg[32 * 32], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      s_last = old == (unsigned)(G - 1) ? 1u : 0u;
-      if (s_last) {
-        cg[32 * 32] = 0u;
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
-    }
-    __syncthreads();
-    if (!s_last) return;
-    for (int i = threadIdx.x; i < nval; i += 256) {
-      double v[32];
-#pragma unroll
-      for (int g = 0; g < 32; ++g) v[g] = fp[(size_t)min(g, G - 1) * nval + i];
-      double s = 0.0;
-#pragma unroll
-      for (int g = 0; g < 32; ++g) s += g < G ? v[g] : 0.0;
-      const int ch = cb0 + (i >> 1);
-      if (i & 1) { a.dgamma[ch] += (float)s; a.coef[2 * ch + 1] = (float)(s / (double)a.npix); }
-      else { a.dbeta[ch] += (float)s; a.coef[2 * ch] = (float)(s / (double)a.npix); }
-    }
-  }
-}
-// MEASURED (round 3, U-Net++/resnet101, one box): slower than the separate finalize launch it replaces -- BatchNorm sweeps alone 12.87 ->
-// 15.67 ms per step at 16 frames, 3.36 -> 5.94 at 2 frames (+22 us per launch: two agent acquires at 4-8 resident workgroups per CU cost
-// ~7 us each, MI355X_MICROARCH.md fence table, plus the ticket round trips; the launch boundary it saves is ~12 us).  Opt-in only.
-bool bn_bwd_fused_finalize() {
-  static const bool on = getenv("OCTSEG_FUSED_BNFIN") != nullptr;   // A/B switch (default: separate bn_bwd_finalize launch)
-  return on;
 }
 hipError_t launch_bn_bwd_reduce(int dtype, const BnBwdArgs& a, hipStream_t st) {
   OCTSEG_NO_F16(dtype);
   const int VEC = dtype == DT_F32 ? 4 : 8;
   const int vpc = a.C / VEC;
   dim3 grid(a.rows, vpc >= 256 ? vpc / 256 : 1);
-  const bool fused = a.fpart != nullptr && a.fcnt != nullptr;
-  if (fused && (grid.y > 8 || a.rows > 1024)) return hipErrorInvalidValue;
-  if (dtype == DT_F32) {
-    if (fused) hipLaunchKernelGGL((bn_bwd_reduce_kernel<float, true>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((bn_bwd_reduce_kernel<float, false>), grid, dim3(256), 0, st, a);
-  } else {
-    if (fused) hipLaunchKernelGGL((bn_bwd_reduce_kernel<bf16_t, true>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((bn_bwd_reduce_kernel<bf16_t, false>), grid, dim3(256), 0, st, a);
-  }
+  if (dtype == DT_F32) hipLaunchKernelGGL(bn_bwd_reduce_kernel<float>, grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(bn_bwd_reduce_kernel<bf16_t>, grid, dim3(256), 0, st, a);
   return hipGetLastError();
 }
 

@@ -43,16 +43,11 @@ struct G1Args {
   const float* bias; int relu_out;       // eval with folded BatchNorm: y = relu?(acc + bias[n])
 };
 
-// BRES: the whole K x BN weight panel of the workgroup's N tile stays in LDS (K <= 256: four slabs, 64 KiB) for all of its M tiles --
-// no per-step weight traffic, NO barrier in the main loop (waves run free: one's epilogue overlaps the others' loads and
-// MFMAs), one workgroup per CU with the whole register file, six K steps of activations in flight per wave.  For the
-// output-heavy layers (N >= 4 tiles: bottleneck conv3, the data gradient of conv1), whose items are only K / 64 <= 4 steps long.
-// NEGATIVE RESULT (round 2), kept opt-in: see g1_geom.
-template <typename T, int NT, bool AFF, bool BRES>
-__global__ __launch_bounds__(256, BRES ? 1 : 2) void gemm1x1_kernel(const G1Args a) {
-  constexpr int D = BRES ? 6 : G1_D;            // K steps of activations in flight per wave
+template <typename T, int NT, bool AFF>
+__global__ __launch_bounds__(256, 2) void gemm1x1_kernel(const G1Args a) {
+  constexpr int D = G1_D;                       // K steps of activations in flight per wave
   constexpr int NSET = D + 1;                   // register sets of the activation ring
-  constexpr int NSLOT = BRES ? 4 : 2;           // weight slabs in LDS
+  constexpr int NSLOT = 2;                      // weight slabs in LDS
   constexpr int BN = NT * 32;
   constexpr int SLAB = BN * 128;                 // bytes of one (K step, N tile) weight slab
   constexpr int NPB = SLAB / 4096;               // 16-byte pieces of the slab per thread (1, 2 or 4)
@@ -138,14 +133,10 @@ __global__ __launch_bounds__(256, BRES ? 1 : 2) void gemm1x1_kernel(const G1Args
   const int bbase = r * 128;
   const unsigned floor16 = a.relu ? 0u : 0x80008000u;
 
-  // ---- prologue: slab 0 into slot 0, slab 1 in registers (BRES: every slab of the panel into its slot), D activation steps in flight
-  if constexpr (BRES) {
-    for (int q = 0; q < S; ++q) { G1_LOAD_B(); G1_STORE_B(q); }
-  } else {
-    G1_LOAD_B();
-    G1_STORE_B(0);
-    G1_LOAD_B();
-  }
+  // ---- prologue: slab 0 into slot 0, slab 1 in registers, D activation steps in flight
+  G1_LOAD_B();
+  G1_STORE_B(0);
+  G1_LOAD_B();
 #pragma unroll
   for (int d = 0; d < D; ++d) load_A(A[d]);
   __syncthreads();
@@ -213,12 +204,10 @@ __global__ __launch_bounds__(256, BRES ? 1 : 2) void gemm1x1_kernel(const G1Args
 
   auto step = [&](auto set_c, int g) __attribute__((always_inline)) {
     constexpr int SET = decltype(set_c)::value;
-    const int slot = BRES ? s : (g & 1);
-    if constexpr (!BRES) {
-      // weights of step g + 1 (in registers since the previous step) into the other slot, then fetch those of step g + 2
-      G1_STORE_B(slot ^ 1);
-      G1_LOAD_B();
-    }
+    const int slot = g & 1;
+    // weights of step g + 1 (in registers since the previous step) into the other slot, then fetch those of step g + 2
+    G1_STORE_B(slot ^ 1);
+    G1_LOAD_B();
     // activations of step g + D
     load_A(A[(SET + D) % NSET]);
     const bool tail = (mt * G1_BM + G1_BM > a.M);
@@ -254,7 +243,7 @@ __global__ __launch_bounds__(256, BRES ? 1 : 2) void gemm1x1_kernel(const G1Args
       s = 0;
       mt += Gm;
     }
-    if constexpr (!BRES) __syncthreads();
+    __syncthreads();
   };
 
   for (int g = 0; g < total; g += NSET) {
@@ -262,13 +251,7 @@ __global__ __launch_bounds__(256, BRES ? 1 : 2) void gemm1x1_kernel(const G1Args
     if (g + 1 < total) step(std::integral_constant<int, 1>{}, g + 1);
     if (g + 2 < total) step(std::integral_constant<int, 2>{}, g + 2);
     if (g + 3 < total) step(std::integral_constant<int, 3>{}, g + 3);
-    if constexpr (NSET > 4) {
-      if (g + 4 < total) step(std::integral_constant<int, 4 % NSET>{}, g + 4);
-      if (g + 5 < total) step(std::integral_constant<int, 5 % NSET>{}, g + 5);
-      if (g + 6 < total) step(std::integral_constant<int, 6 % NSET>{}, g + 6);
-    }
   }
-  if constexpr (BRES) __syncthreads();   // the strips double as the reduction buffer below
 
 #undef G1_LOAD_B
 #undef G1_STORE_B
@@ -294,7 +277,7 @@ __global__ __launch_bounds__(256, BRES ? 1 : 2) void gemm1x1_kernel(const G1Args
 
 namespace {
 
-struct G1Geom { int NT, n_tiles, m_tiles, G, rows, bres; size_t lds; };
+struct G1Geom { int NT, n_tiles, m_tiles, G, rows; size_t lds; };
 
 static G1Geom g1_geom(const ConvArgs& a) {
   G1Geom g;
@@ -303,25 +286,20 @@ static G1Geom g1_geom(const ConvArgs& a) {
   g.n_tiles = (a.Cout + BN - 1) / BN;
   const long long M = (long long)a.N * a.OH * a.OW;
   g.m_tiles = (int)((M + G1_BM - 1) / G1_BM);
-  // opt-in (OCTSEG_G1_BRES=1): measured SLOWER than the streaming form on U-Net++/resnet101 (bottleneck conv3 forward 1.97 -> 2.66 ms
-  // per step, conv1 data gradients 1.74 -> 2.24): four waves per CU do not cover the HBM latency that eight (two workgroups) do
-  static const bool use_bres = getenv("OCTSEG_G1_BRES") != nullptr;
-  g.bres = (use_bres && g.NT == 4 && a.Cin <= 256 && a.Cin >= 128 && g.n_tiles >= 4) ? 1 : 0;
-  int gm = (g.bres ? G1_MAXWG / 2 : G1_MAXWG) / g.n_tiles;   // BRES: one workgroup per CU
+  int gm = G1_MAXWG / g.n_tiles;
   if (gm < 1) gm = 1;
   if (gm > g.m_tiles) gm = g.m_tiles;
   g.rows = gm;
   g.G = gm * g.n_tiles;
   const bool aff = a.src[0].scale != nullptr;
-  g.lds = (size_t)(g.bres ? 4 : 2) * BN * 128 + (size_t)4 * 32 * (BN * 2 + 16) + (aff ? (size_t)a.Cin * 8 : 0);
+  g.lds = (size_t)2 * BN * 128 + (size_t)4 * 32 * (BN * 2 + 16) + (aff ? (size_t)a.Cin * 8 : 0);
   return g;
 }
 
 }  // namespace
 
 bool gemm1x1_eligible(const ConvArgs& a, int dtype) {
-  static const bool off = getenv("OCTSEG_NO_GEMM1X1") != nullptr;   // A/B switch
-  if (off || dtype == DT_F32) return false;
+  if (dtype == DT_F32) return false;
   if (a.ntaps != 1 || a.istride != 1 || a.ostride != 1 || a.out_mode == OUT_HEAD_NCHW) return false;
   if (a.tap_dy[0] != 0 || a.tap_dx[0] != 0 || a.nsrc != 1 || a.ndst != 1) return false;
   if (a.bias != nullptr && a.stat_slab != nullptr) return false;   // (bias only as the folded BatchNorm shift of eval forwards)
@@ -336,23 +314,20 @@ bool gemm1x1_eligible(const ConvArgs& a, int dtype) {
 
 int gemm1x1_rows(const ConvArgs& a) { return g1_geom(a).rows; }
 
-template <typename T, int NT, bool AFF, bool BRES>
+template <typename T, int NT, bool AFF>
 static hipError_t g1_launch_k(const G1Args& ga, const G1Geom& g, hipStream_t st) {
   static bool set = false;
   if (!set) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm1x1_kernel<T, NT, AFF, BRES>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipError_t e = hipFuncSetAttribute((const void*)gemm1x1_kernel<T, NT, AFF>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) return e;
     set = true;
   }
-  hipLaunchKernelGGL((gemm1x1_kernel<T, NT, AFF, BRES>), dim3(g.G), dim3(256), g.lds, st, ga);
+  hipLaunchKernelGGL((gemm1x1_kernel<T, NT, AFF>), dim3(g.G), dim3(256), g.lds, st, ga);
   return hipGetLastError();
 }
 template <typename T, int NT>
 static hipError_t g1_launch(const G1Args& ga, const G1Geom& g, bool aff, hipStream_t st) {
-  if constexpr (NT == 4) {
-    if (g.bres) return aff ? g1_launch_k<T, NT, true, true>(ga, g, st) : g1_launch_k<T, NT, false, true>(ga, g, st);
-  }
-  return aff ? g1_launch_k<T, NT, true, false>(ga, g, st) : g1_launch_k<T, NT, false, false>(ga, g, st);
+  return aff ? g1_launch_k<T, NT, true>(ga, g, st) : g1_launch_k<T, NT, false>(ga, g, st);
 }
 
 hipError_t launch_gemm1x1(int dtype, const ConvArgs& a, hipStream_t st) {

@@ -9,11 +9,8 @@ namespace detail {
 // all 256 CUs with one long-running workgroup each (110-150 KB of LDS, 380 registers) leaves the data gradient and the BatchNorm sweeps of the
 // chain nothing to start on until its workgroups retire; on 144-160 CUs it takes 30 % longer by itself (24.5 against 18.9 ms per step at 160, alone)
 // and the step gets shorter: 65.1 -> 63.0 ms at 144 workgroups (ABAB on one box; 112: 67.8, 128: 63.5, 136: 63.0, 152: 63.3, 160: 63.4-63.7, 176: 63.7).  On the caller's own stream (one-stream
-// mode, the kernels-alone pass of bench.py) nothing runs beside it and it keeps the full width.  OCTSEG_WGRAD_SIDE_WGS=n (A/B; 256 = full width).
-static int side_wgs() {
-  static const int v = getenv("OCTSEG_WGRAD_SIDE_WGS") ? atoi(getenv("OCTSEG_WGRAD_SIDE_WGS")) : 144;
-  return v;
-}
+// mode, the kernels-alone pass of bench.py) nothing runs beside it and it keeps the full width (wg_target = 0).
+static int side_wgs() { return 144; }
 
 // BN backward of BN `bn` over raw tensor y: g -> dy (written to grad(y))
 static int bn_backward(Exec& E, int bn, const void* g, int mask, const void* out_mask, void* res_grad = nullptr, int res_store = 0,
@@ -35,17 +32,13 @@ static int bn_backward(Exec& E, int bn, const void* g, int mask, const void* out
   size_t rows = (a.npix + tpv - 1) / tpv;
   // slab rows = workgroups of the reduce pass (<= 1024: the slab's size).  Measured on U-Net++/resnet101: 256 rows everywhere +1.7 % at
   // --batch 2, +-0 at 4, -2 % at 16; 64 rows -9 % at 2; a size rule (256 rows up to 4 M elements) moved nothing: 1024 stays.
-  static const size_t rows_env = getenv("OCTSEG_BN_ROWS") ? (size_t)atoi(getenv("OCTSEG_BN_ROWS")) : 0;   // experiments
-  const size_t rows_cap = rows_env ? rows_env : 1024;
-  if (rows > rows_cap) rows = rows_cap;
+  if (rows > 1024) rows = 1024;
   a.rows = (int)rows;
   a.dgamma = E.grads + P->params[b.gamma].off;
   a.dbeta = E.grads + P->params[b.beta].off;
   a.coef = E.bn_coef(bn);
   a.dy = E.grad(b.y);
   a.res_grad = res_grad; a.res_store = res_store;
-  const bool fused_fin = bn_bwd_fused_finalize();   // the reduce kernel finishes the reduction itself: no finalize launch
-  if (fused_fin) { a.fpart = (double*)(E.ws + P->bwd_part_off); a.fcnt = (unsigned*)(E.ws + P->bwd_cnt_off); }
   E.ginit[b.y] = 1;   // written (stored) by the apply pass below
   const double tbytes = (double)a.npix * b.C * dtype_size(P->dtype);   // class 3 = HBM-bound sweeps: "flops" carries algorithmic bytes
   if (a.npix <= (size_t)BN_SMALL_COUNT) {   // small tensors: reduce, finalize and apply in one launch, in double (elementwise.hip)
@@ -57,7 +50,7 @@ static int bn_backward(Exec& E, int bn, const void* g, int mask, const void* out
       ProfScope ps(3, tbytes * ((mask == 2 && !maskbits) ? 3 : 2), E.st, b.name + ".bwd_reduce");
       HIPCHK(launch_bn_bwd_reduce(P->dtype, a, E.st));
     }
-    if (!fused_fin) HIPCHK(launch_bn_bwd_finalize(a, E.st));
+    HIPCHK(launch_bn_bwd_finalize(a, E.st));
   }
   {
     ProfScope ps(3, tbytes * (((mask == 2 && !maskbits) ? 4 : 3) + (res_grad ? (res_store ? 1 : 2) : 0)), E.st, b.name + ".bwd_apply");
@@ -93,11 +86,10 @@ static int conv_backward(Exec& E, const ConvLayer& L, const void* dy, int dyC) {
     HIPCHK(launch_stem_im2col(P->dtype, P->stem_image, E.act(P->col_tensor), P->B, P->H, P->W, tc.C, P->stem_mean, P->stem_std,
                               P->stem_normalize, ws_));
   }
-  // The weight gradient depends on dy and on saved activations only: forked in front of the layer's data gradient.  OCTSEG_WGRAD_BEHIND (A/B):
-  // forked behind it, so that it would start together with the BatchNorm sweeps of the layer below (HBM-bound; at <= 128 registers they fit
-  // beside its one-wave-per-SIMD workgroups) -- measured 70.2 against 68.5 ms per step (round 4, ABAB on one box; round 2: 78.8 against 78.4):
-  // the side stream then idles through every data gradient's first half and the step's tail grows.
-  static const bool wgrad_first = getenv("OCTSEG_WGRAD_BEHIND") == nullptr;
+  // The weight gradient depends on dy and on saved activations only: forked in front of the layer's data gradient.  Forked behind it, so
+  // that it would start together with the BatchNorm sweeps of the layer below (HBM-bound; at <= 128 registers they fit beside its
+  // one-wave-per-SIMD workgroups), measured 70.2 against 68.5 ms per step (round 4, ABAB on one box; round 2: 78.8 against 78.4): the side
+  // stream then idles through every data gradient's first half and the step's tail grows.
   auto wgrad_part = [&]() -> int {
     // weight gradient (+ bias gradient) on the side stream: fork after everything that produced dy
     hipStream_t ws_ = E.wst ? E.wst : E.st;
@@ -181,14 +173,11 @@ static int conv_backward(Exec& E, const ConvLayer& L, const void* dy, int dyC) {
       const TensorInfo& t0 = P->tensors[ti0];
       const double macs = layer_macs(L);
       std::vector<ConvArgs> lu;
-      const bool planes = tie_dgrad_planes() && !L.tie_du_masked;
       if (L.tie_du_masked) { lu.resize(1); tied_dgrad_masked(tie_geom_up(L), lu[0]); }
-      else if (planes) tied_dgrad_launches(tie_geom_up(L), lu);
       else dgrad_launches(tie_geom_up(L), lu);   // (one launch: 16 taps at stride 2 over dy)
       const int acc0 = E.claim(ti0);
       for (int k = 0; k < (int)lu.size(); ++k) {
         ConvArgs& a = lu[k];
-        const int py = k >> 1, px = k & 1;
         if (L.tie_du_masked) {
           for (int p = 0; p < 4; ++p) {   // plane p of dy as a tensor of its own: first pixel (p >> 1, p & 1), doubled pixel and row strides
             SrcDesc& s = a.src[p];
@@ -197,8 +186,7 @@ static int conv_backward(Exec& E, const ConvLayer& L, const void* dy, int dyC) {
           }
         } else {
           SrcDesc s;
-          s.ptr = (const char*)dy + (planes ? ((size_t)py * L.OW + px) * dyC * esz : 0);
-          s.scale = nullptr; s.shift = nullptr; s.C = planes ? 2 * dyC : dyC; s.c0 = 0; s.H = planes ? L.OH / 2 : L.OH; s.W = L.OW; s.up = 0; s.relu = 0;
+          s.ptr = dy; s.scale = nullptr; s.shift = nullptr; s.C = dyC; s.c0 = 0; s.H = L.OH; s.W = L.OW; s.up = 0; s.relu = 0;
           a.src[0] = s; a.nsrc = 1;
           a.Cin = L.Cout;
         }
@@ -250,8 +238,7 @@ static int conv_backward(Exec& E, const ConvLayer& L, const void* dy, int dyC) {
       const size_t soff = (size_t)L.srcs[i].c0 * esz;
       DstDesc d;
       d.C = t.C; d.c0 = c0; d.cn = scn; d.H = L.IH; d.W = L.IW; d.accum = 0; d.pool = 0;
-      static const bool no_fuse_pool = getenv("OCTSEG_NO_FUSED_POOL") != nullptr;
-      if (L.srcs[i].up && t.need_grad && !no_fuse_pool && ld.size() == 1 && ld[0].ostride == 1 && (L.IH % 2) == 0 && (L.IW % 2) == 0) {
+      if (L.srcs[i].up && t.need_grad && ld.size() == 1 && ld[0].ostride == 1 && (L.IH % 2) == 0 && (L.IW % 2) == 0) {
         // gradient of the nearest-x2 upsample: the dgrad epilogue sums the 2x2 quads straight into the source's gradient
         d.ptr = E.grad(ti); d.H = t.H; d.W = t.W; d.pool = 1;
         d.accum = E.claim(ti);
@@ -299,10 +286,8 @@ static int conv_backward(Exec& E, const ConvLayer& L, const void* dy, int dyC) {
     }
     return OCTSEG_OK;
   };
-  if (wgrad_first) { const int rc = wgrad_part(); if (rc) return rc; }
-  { const int rc = dgrad_part(); if (rc) return rc; }
-  if (!wgrad_first) { const int rc = wgrad_part(); if (rc) return rc; }
-  return OCTSEG_OK;
+  { const int rc = wgrad_part(); if (rc) return rc; }
+  return dgrad_part();
 }
 
 // The loss kernels' arguments without the forward's outputs (octseg_dice_forward and the training step add `stats` and `loss`).
@@ -369,10 +354,8 @@ int run_backward(Exec& E, const float* logits, const float* target, float grad_s
   };
   HIPCHK(hipMemsetAsync(E.grads, 0, P->param_numel * sizeof(float), E.st));
   HIPCHK(hipMemsetAsync(E.ws + P->fin_cnt_off, 0, 2 * 64 * sizeof(unsigned), E.st));
-  HIPCHK(hipMemsetAsync(E.ws + P->bwd_cnt_off, 0, 8 * 33 * 32 * sizeof(unsigned), E.st));
   E.ginit.assign(P->tensors.size(), 0);
-  static const bool no_side = getenv("OCTSEG_NO_SIDE_STREAM") != nullptr;   // A/B switch
-  if (!no_side && !serial_mode()) {
+  if (!serial_mode()) {
     // (a step that is being captured / replayed as one hipGraph keeps the default priority: replaying a graph whose side branch was captured
     //  from a lowest-priority stream took 34.9 instead of 20.7 ms per step at 2 frames, profiles/r4_graph_ab.txt)
     hipStream_t* wsp = P->tgraph_enabled ? &P->side : &P->side_bwd;
@@ -418,8 +401,7 @@ int run_backward(Exec& E, const float* logits, const float* target, float grad_s
         const int mask = !op.relu ? 0 : (op.post >= 0 ? 1 : 2);
         // identity shortcut of a residual block (no BatchNorm on it, ReLU mask from the block's output): its gradient G * mask is
         // written by the main branch's apply sweep, which holds G and the mask already (was a masked_accum pass of its own)
-        static const bool no_fuse_res = getenv("OCTSEG_NO_FUSED_RESGRAD") != nullptr;   // A/B switch
-        const bool fuse_res = !no_fuse_res && mask == 2 && op.res.t >= 0 && op.res.bn < 0 && P->tensors[op.res.t].need_grad &&
+        const bool fuse_res = mask == 2 && op.res.t >= 0 && op.res.bn < 0 && P->tensors[op.res.t].need_grad &&
                               E.grad(op.res.t) != G && E.grad(op.res.t) != E.grad(P->bns[op.y.bn].y);
         const unsigned char* mbits = (mask == 2 && t.mask_off) ? (const unsigned char*)(E.ws + t.mask_off) : nullptr;
         if (fuse_res) {

@@ -617,8 +617,7 @@ static void assign_lanes(octseg_plan* P) {
     const std::string nm = op_name(P->ops[i]);
     if (nm.rfind("decoder.", 0) == 0 || nm.rfind("segmentation_head", 0) == 0) { enc_end = i; break; }
   }
-  const char* lane_stage = getenv("OCTSEG_LANE_STAGE");   // experiments: encoder stage the side lane may not depend on
-  const std::string stage = std::string("encoder.") + (lane_stage ? lane_stage : "layer4") + ".";
+  const std::string stage = "encoder.layer4.";   // the encoder stage the side lane may not depend on
   for (int i = 0; i < enc_end; ++i)
     if (op_name(P->ops[i]).rfind(stage, 0) == 0) { l3_begin = i; break; }
   if (enc_end >= n || l3_begin < 0) return;
@@ -917,15 +916,12 @@ int build_plan(octseg_plan* P) {
   for (auto& t : P->tensors)
     if (t.need_grad && t.grad_alias >= 0) t.goff = P->tensors[t.grad_alias].goff;
   P->grad_end = off;
-  {
-    static const bool no_bits = getenv("OCTSEG_NO_MASKBITS") != nullptr;   // A/B switch: the backward re-reads the output tensor for the mask
-    for (auto& op : P->ops)
-      if (!no_bits && op.kind == OP_BN_ACT && op.relu && op.post < 0) {
-        TensorInfo& t = P->tensors[op.out];
-        const size_t nvec = (size_t)t.N * t.H * t.W * t.C * esz / 16;
-        t.mask_off = off; off += align_up(nvec);
-      }
-  }
+  for (auto& op : P->ops)
+    if (op.kind == OP_BN_ACT && op.relu && op.post < 0) {
+      TensorInfo& t = P->tensors[op.out];
+      const size_t nvec = (size_t)t.N * t.H * t.W * t.C * esz / 16;
+      t.mask_off = off; off += align_up(nvec);
+    }
   for (auto& g : P->gns) {
     const TensorInfo& t = P->tensors[g.y];
     const size_t S = (size_t)gn_num_slabs((size_t)t.H * t.W);
@@ -977,13 +973,13 @@ int build_plan(octseg_plan* P) {
         L.tie_fu_off = off; off += align_up(conv_image_bytes(L.tie_pk_fu, 16));
         v.clear();
         L.tie_du_masked = false;
-        if (!tie_dgrad_planes() && L.Cout % 64 == 0) {   // one masked launch over the four parity planes: the planes are whole K chunks
+        if (L.Cout % 64 == 0) {   // one masked launch over the four parity planes: the planes are whole K chunks
           ConvArgs am;
           tied_dgrad_masked(gu, am);
           DstDesc dd{}; dd.H = gu.IH; dd.W = gu.IW; dd.C = Ca; dd.cn = Ca; am.dst[0] = dd; am.ndst = 1;
           if (conv_masked_eligible(am, P->dtype)) { L.tie_du_masked = true; v.push_back(am); }
         }
-        if (!L.tie_du_masked) { if (tie_dgrad_planes()) tied_dgrad_launches(gu, v); else dgrad_launches(gu, v); }
+        if (!L.tie_du_masked) dgrad_launches(gu, v);
         L.tie_pk_du = conv_pack_info(v[0], P->dtype);
         L.tie_du_off = off; off += align_up(conv_image_bytes(L.tie_pk_du, L.tie_du_masked ? 9 : 16));
         if (Cs > 0) {
@@ -1075,8 +1071,6 @@ int build_plan(octseg_plan* P) {
   P->slab_off = off; P->slab_bytes = align_up(slab); off += 2 * align_up(slab);          // one slab per forward lane
   P->fin_part_off = off; off += 2 * align_up((size_t)SLAB_PART_CAP * 2 * sizeof(double));   // two-level slab reduction scratch (per lane)
   P->fin_cnt_off = off; off += align_up(2 * 64 * sizeof(unsigned));
-  P->bwd_part_off = off; off += align_up((size_t)8 * 32 * 4096 * sizeof(double));   // [column][group][256 vectors x 8 channels x 2]
-  P->bwd_cnt_off = off; off += align_up((size_t)8 * 33 * 32 * sizeof(unsigned));   // one 128-byte line per ticket
   {
     size_t pool_elems = 0;
     for (auto& op : P->ops)

@@ -25,15 +25,13 @@ hipEvent_t prof_event() {
 // B = 1 replay, whose lanes ARE its critical path, fell from 148 to 121 frames/s) and the backward's weight gradients.  The latter's stream is
 // created with the LOWEST priority: the chain's kernels win the dispatch whenever compute units free up, the weight gradients fill what is
 // left (round 4, ABAB on one box, eager steps: 67.75-68.0 ms per step against 68.2-68.3 at the default priority, 69.1 at the highest; under
-// graph replay round 3 saw no difference).  OCTSEG_SIDE_PRIORITY=normal|high|low sets both (A/B switch).
+// graph replay round 3 saw no difference).
 hipError_t create_side_stream(hipStream_t* st, bool backward) {
-  static const char* pr = getenv("OCTSEG_SIDE_PRIORITY");
-  const char mode = pr != nullptr ? pr[0] : (backward ? 'l' : 'n');
-  if (mode == 'l' || mode == 'h') {
+  if (backward) {
     int least = 0, greatest = 0;
     hipError_t e = hipDeviceGetStreamPriorityRange(&least, &greatest);
     if (e != hipSuccess) return e;
-    return hipStreamCreateWithPriority(st, hipStreamNonBlocking, mode == 'l' ? least : greatest);
+    return hipStreamCreateWithPriority(st, hipStreamNonBlocking, least);
   }
   // (a side stream confined to a share of the compute units -- hipExtStreamCreateWithCUMask, 6 / 4 / 7 of every 8 CUs -- so that the caller's
   //  stream always finds free CUs for its sweeps: 75.2 -> 91.7 ms per step whatever the share; measured once, not kept)
@@ -124,8 +122,7 @@ int run_forward(Exec& E, const float* image, float* logits, int normalize, const
   const bool folded = !E.train;
   // ---- forward lanes (assign_lanes): lane-1 ops go to the side stream; a lane waits for the other one only when it
   // reads something the other lane produced and has not synchronised with since
-  static const bool no_lanes = getenv("OCTSEG_NO_FWD_LANES") != nullptr;
-  const bool lanes = P->has_lanes && !no_lanes && !serial_mode();
+  const bool lanes = P->has_lanes && !serial_mode();
   hipStream_t lst[2] = {E.st, E.st};
   if (lanes) {
     // training forwards share the backward's lowest-priority stream (the second lane yields to the encoder chain: 69.1 / 68.6 against 69.7 /

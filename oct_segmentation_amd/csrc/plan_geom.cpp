@@ -128,34 +128,8 @@ void wgrad_launches(const Geom& g, std::vector<WgradArgs>& out) {
   }
 }
 
-// Data gradient of the tied ConvTranspose2d (Geom of the ConvT: IH x IW = the low-resolution map): the adjoint of each forward parity launch is a
-// stride-1 2x2-tap conv over ONE parity plane of dy (the caller presents the plane as a tensor of its own: pointer offset, doubled pixel and row
-// strides), all four accumulating into the low-resolution gradient.  Four launches of 4 taps over 176^2 planes instead of one 16-tap stride-2
-// launch whose 34 x 34 window does not fit a double-buffered LDS tile.  out[k] belongs to parity (k >> 1, k & 1).
-void tied_dgrad_launches(const Geom& g, std::vector<ConvArgs>& out) {
-  for (int py = 0; py < 2; ++py)
-    for (int px = 0; px < 2; ++px) {
-      ConvArgs a;
-      memset(&a, 0, sizeof(a));
-      int n = 0;
-      for (int r = 0; r < g.R; ++r) {
-        if (((py + g.pad - r) & 1) != 0) continue;
-        for (int s = 0; s < g.S; ++s) {
-          if (((px + g.pad - s) & 1) != 0) continue;
-          a.tap_dy[n] = -((py + g.pad - r) / 2); a.tap_dx[n] = -((px + g.pad - s) / 2); a.tap_w[n] = r * g.S + s; ++n;
-        }
-      }
-      set_taps(a.tap_dy, a.tap_dx, a.tap_w, n, a.ntaps, a.min_dy, a.min_dx, a.span_y, a.span_x);
-      a.istride = 1; a.N = g.N; a.IH = g.IH; a.IW = g.IW; a.OH = g.IH; a.OW = g.IW;
-      a.Cin = g.Cout; a.Cout = g.Cin; a.ostride = 1;
-      out.push_back(a);
-    }
-}
-
-// A/B switch: the tied data gradient as four 2x2-tap launches over dy's parity planes instead of one 16-tap stride-2 launch over dy
-bool tie_dgrad_planes() { return getenv("OCTSEG_TIED_DGRAD_PLANES") != nullptr; }
-
-// ... and as ONE stride-1 launch whose four sources are dy's parity planes (virtual channels [p O, (p + 1) O) = plane p), every plane contracting
+// Data gradient of the tied ConvTranspose2d (Geom of the ConvT: IH x IW = the low-resolution map) as ONE stride-1 launch whose four sources are
+// dy's parity planes (virtual channels [p O, (p + 1) O) = plane p), every plane contracting
 // with its own 2 x 2 of the 3 x 3 tap offsets (ConvArgs::taps_per_src, conv_mfma.hip's masked loop): plane (py, px) at offset (dy, dx) carries
 // kernel tap r = py + 1 + 2 dy, s = px + 1 + 2 dx where that lies in [0, 3].  Sources (pointers, strides) are filled by the caller.
 void tied_dgrad_masked(const Geom& g, ConvArgs& a) {

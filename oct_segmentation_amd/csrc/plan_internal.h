@@ -62,9 +62,7 @@ struct Geom {
 void fwd_launches(const Geom& g, std::vector<ConvArgs>& out);
 void dgrad_launches(const Geom& g, std::vector<ConvArgs>& out);
 void wgrad_launches(const Geom& g, std::vector<WgradArgs>& out);
-void tied_dgrad_launches(const Geom& g, std::vector<ConvArgs>& out);
 void tied_dgrad_masked(const Geom& g, ConvArgs& a);
-bool tie_dgrad_planes();
 int tie_mask();
 Geom tie_geom_up(const ConvLayer& L);
 Geom tie_geom_skip(const ConvLayer& L);

@@ -560,14 +560,6 @@ __global__ __launch_bounds__(THIN_NTHR, 2) void thin_wgrad_kernel(const ThinArgs
 // ---------------------------------------------------------------------------------------------------------------- host side
 namespace {
 
-static bool thin_on() {
-  static const bool on = getenv("OCTSEG_NO_THIN") == nullptr;   // A/B switch
-  return on;
-}
-static bool thin_ext_on() {
-  static const bool on = getenv("OCTSEG_NO_THIN_EXT") == nullptr;   // A/B switch: 1x1 / ConvT-parity / stem kinds (round 3)
-  return on && thin_on();
-}
 // tap offsets relative to a window whose origin sits `halo` pixels above / left of the tile
 static int thin_kind(const int* tdy, const int* tdx, int ntaps, int istride, int ostride) {
   if (istride != 1) return -1;
@@ -580,7 +572,6 @@ static int thin_kind(const int* tdy, const int* tdx, int ntaps, int istride, int
     }
     return seen == 0x1ffu ? K33 : -1;
   }
-  if (!thin_ext_on()) return -1;
   if (ntaps == 1 && ostride == 1 && tdy[0] == 0 && tdx[0] == 0) return K11;
   if (ntaps == 4 && ostride == 2) {
     for (int t = 0; t < 4; ++t) if (tdy[t] < -1 || tdy[t] > 1 || tdx[t] < -1 || tdx[t] > 1) return -1;
@@ -623,7 +614,7 @@ static void thin_fill_taps(ThinArgs& ta, const int* tdy, const int* tdx, const i
 }  // namespace
 
 bool thin_conv_eligible(const ConvArgs& a, int dtype) {
-  if (!thin_on() || dtype == DT_F32 || a.Wmaster == nullptr) return false;
+  if (dtype == DT_F32 || a.Wmaster == nullptr) return false;
   if (a.nsrc != 1 || a.ndst != 1) return false;
   const int kind = thin_kind(a.tap_dy, a.tap_dx, a.ntaps, a.istride, a.ostride);
   if (kind < 0) return false;
@@ -675,7 +666,7 @@ hipError_t launch_thin_conv(int dtype, const ConvArgs& a, hipStream_t st) {
 }
 
 bool thin_wgrad_eligible(const WgradArgs& a, int dtype) {
-  if (!thin_on() || dtype != DT_BF16 || deterministic_mode()) return false;
+  if (dtype != DT_BF16 || deterministic_mode()) return false;
   if (a.dstride != 1 || a.doy != 0 || a.dox != 0 || a.nsrc != 1) return false;
   const int kind = thin_kind(a.tap_dy, a.tap_dx, a.ntaps, a.istride, 1);
   if (kind != K33 && kind != K11) return false;
@@ -728,11 +719,10 @@ hipError_t launch_thin_wgrad(int dtype, const WgradArgs& a, hipStream_t st) {
 }
 
 // ---- the ResNet stem (conv 7x7 stride 2 pad 3, 3 -> 64) on the NCHW f32 frame
-bool thin_stem_eligible(int dtype) { return thin_ext_on() && dtype != DT_F32; }
+bool thin_stem_eligible(int dtype) { return dtype != DT_F32; }
 static ThinGeom stem_geom(int N, int H, int W) {   // ~225 registers per lane: two workgroups per CU, one resident round
-  static const int gcap = getenv("OCTSEG_STEM_G") ? atoi(getenv("OCTSEG_STEM_G")) : 512;   // experiments
   ThinGeom g = thin_geom(N, H / 2, W / 2, 4);
-  if (g.G > gcap) g.G = gcap;
+  if (g.G > 512) g.G = 512;
   return g;
 }
 int thin_stem_rows(int N, int H, int W) { return stem_geom(N, H, W).G; }

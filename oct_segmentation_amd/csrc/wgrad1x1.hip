@@ -43,14 +43,13 @@ struct Wgrad1x1Args {
   int co_fast;                            // co tiles fastest in the XCD-local order (speed only)
 };
 
-// DEEP = 0: ring of 3 x 24 KB (MB = 2) / 4 x 16 KB (MB = 1), two workgroups per CU; DEEP = 1: 6 x 24 KB / 8 x 16 KB, one workgroup per CU
-// (half the workgroups = half the split-K atomic traffic, which runs at 1.3 TB/s chip-wide, memory side)
-template <int MB, bool DEEP> struct W1Ring { static constexpr int NST = (MB == 2 ? 3 : 4) * (DEEP ? 2 : 1); };
+// ring of 3 x 24 KB (MB = 2) / 4 x 16 KB (MB = 1), two workgroups per CU
+template <int MB> struct W1Ring { static constexpr int NST = MB == 2 ? 3 : 4; };
 
-template <int MB, bool AFF, bool DEEP>
+template <int MB, bool AFF>
 __global__ __launch_bounds__(256) void wgrad1x1_kernel(const Wgrad1x1Args a) {
   extern __shared__ __attribute__((aligned(1024))) char smem[];
-  constexpr int NST = W1Ring<MB, DEEP>::NST;
+  constexpr int NST = W1Ring<MB>::NST;
   constexpr int D = NST - 1;                      // stages in flight
   constexpr int NPL = MB + 1;                     // planes per stage: MB of dy, one of x
   constexpr int STAGE = NPL * W1_PLANE;
@@ -255,14 +254,9 @@ __global__ __launch_bounds__(256) void wgrad1x1_kernel(const Wgrad1x1Args a) {
   }
 }
 
-static bool wgrad1x1_enabled() {
-  static const bool off = getenv("OCTSEG_NO_WGRAD1X1") != nullptr;   // A/B switch
-  return !off;
-}
-
 // `a` must already be flattened by flatten_1x1 (wgrad_mfma.hip): N = 1, OW = 16 = every W, OH = rows
 bool wgrad1x1_eligible(const WgradArgs& a, int dtype) {
-  if (!wgrad1x1_enabled() || dtype != DT_BF16) return false;
+  if (dtype != DT_BF16) return false;
   if (a.ntaps != 1 || a.istride != 1 || a.dstride != 1 || a.tap_dy[0] != 0 || a.tap_dx[0] != 0 || a.doy != 0 || a.dox != 0) return false;
   if (a.N != 1 || a.OW != TW || a.IW != TW || a.DW != TW || a.IH != a.OH || a.DH != a.OH) return false;
   if (a.Cin % 64 != 0 || a.Cout % 64 != 0 || a.dyC % 8 != 0 || a.Cout > a.dyC) return false;
@@ -278,17 +272,17 @@ bool wgrad1x1_eligible(const WgradArgs& a, int dtype) {
   return true;
 }
 
-template <int MB, bool AFF, bool DEEP>
+template <int MB, bool AFF>
 static hipError_t launch_w1(const Wgrad1x1Args& a, int gx, int gy, int gz, hipStream_t st) {
-  constexpr int NST = W1Ring<MB, DEEP>::NST;
+  constexpr int NST = W1Ring<MB>::NST;
   constexpr size_t lds = (size_t)NST * (MB + 1) * W1_PLANE;
   static bool attr_set = false;
   if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)wgrad1x1_kernel<MB, AFF, DEEP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipError_t e = hipFuncSetAttribute((const void*)wgrad1x1_kernel<MB, AFF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     attr_set = true;
   }
-  hipLaunchKernelGGL((wgrad1x1_kernel<MB, AFF, DEEP>), dim3(gx, gy, gz), dim3(256), lds, st, a);
+  hipLaunchKernelGGL((wgrad1x1_kernel<MB, AFF>), dim3(gx, gy, gz), dim3(256), lds, st, a);
   return hipGetLastError();
 }
 
@@ -306,11 +300,7 @@ hipError_t launch_wgrad1x1(int dtype, const WgradArgs& w, hipStream_t st) {
   const long long ns_total = (a.P + W1_SP - 1) / W1_SP;
   // split-K: two workgroups per CU in one resident round; every workgroup ends by adding its tile to dW with atomics (ksplit x the
   // size of dW in atomic traffic), so no more ranges than that -- and at least 4 stages per range, or the ring never fills
-  static const int wg_env = getenv("OCTSEG_WGRAD1X1_WGS") ? atoi(getenv("OCTSEG_WGRAD1X1_WGS")) : 0;
-  static const int deep_env = getenv("OCTSEG_WGRAD1X1_DEEP") ? atoi(getenv("OCTSEG_WGRAD1X1_DEEP")) : -1;
-  const bool deep = deep_env >= 0 ? deep_env != 0 : false;
-  const int wg_target = wg_env > 0 ? wg_env : (deep ? 256 : 512);
-  long long ks = wg_target / (gx * gy);
+  long long ks = 512 / (gx * gy);
   if (ks > ns_total / 4) ks = ns_total / 4;
   if (ks < 1) ks = 1;
   if (deterministic_mode()) ks = 1;      // one writer per dW element: a fixed summation order
@@ -319,12 +309,8 @@ hipError_t launch_wgrad1x1(int dtype, const WgradArgs& w, hipStream_t st) {
   a.spw = (int)spw;
   static const bool ci_major = getenv("OCTSEG_WGRAD_CI_MAJOR") != nullptr;   // A/B switch
   a.co_fast = ci_major ? 0 : 1;
-  if (deep) {
-    if (MB == 2) return aff ? launch_w1<2, true, true>(a, gx, gy, (int)ks, st) : launch_w1<2, false, true>(a, gx, gy, (int)ks, st);
-    return aff ? launch_w1<1, true, true>(a, gx, gy, (int)ks, st) : launch_w1<1, false, true>(a, gx, gy, (int)ks, st);
-  }
-  if (MB == 2) return aff ? launch_w1<2, true, false>(a, gx, gy, (int)ks, st) : launch_w1<2, false, false>(a, gx, gy, (int)ks, st);
-  return aff ? launch_w1<1, true, false>(a, gx, gy, (int)ks, st) : launch_w1<1, false, false>(a, gx, gy, (int)ks, st);
+  if (MB == 2) return aff ? launch_w1<2, true>(a, gx, gy, (int)ks, st) : launch_w1<2, false>(a, gx, gy, (int)ks, st);
+  return aff ? launch_w1<1, true>(a, gx, gy, (int)ks, st) : launch_w1<1, false>(a, gx, gy, (int)ks, st);
 }
 
 }  // namespace octseg

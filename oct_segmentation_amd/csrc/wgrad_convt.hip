@@ -278,8 +278,7 @@ __global__ __launch_bounds__(NTHR) void wgrad_convt16_kernel(const WgradArgs a) 
 
 // `a`: any of the four parity launches of wgrad_launches' transposed form (sources, extents, dy, dW are the same in all four)
 bool wgrad_convt16_eligible(const WgradArgs& a, int dtype) {
-  static const bool off = getenv("OCTSEG_NO_WGRAD_CONVT16") != nullptr;   // A/B switch: four per-parity launches
-  if (off || dtype != DT_BF16) return false;
+  if (dtype != DT_BF16) return false;
   if (a.ntaps != 4 || a.istride != 1 || a.dstride != 2 || a.span_x != 2 || a.span_y != 2) return false;
   if (a.OH != a.IH || a.OW != a.IW || a.DH != 2 * a.IH || a.DW != 2 * a.IW) return false;
   if (a.Cin % 8 != 0 || a.dyC % 8 != 0 || a.Cin < 32 || a.Cout < 32) return false;
@@ -295,8 +294,7 @@ hipError_t launch_wgrad_convt16(int dtype, const WgradArgs& a0, hipStream_t st) 
   WgradArgs a = a0;
   const int ntiles = a.N * ((a.OW + TW - 1) / TW) * ((a.OH + CT_TH - 1) / CT_TH);
   const int gx = (a.Cin + 63) / 64, gy = (a.Cout + 63) / 64;
-  static const int wg_env = getenv("OCTSEG_WGRAD_WGS") ? atoi(getenv("OCTSEG_WGRAD_WGS")) : 0;   // experiments
-  int ks = (wg_env > 0 ? wg_env : (a.wg_target > 0 ? a.wg_target : 256)) / (gx * gy);
+  int ks = (a.wg_target > 0 ? a.wg_target : 256) / (gx * gy);
   if (ks > ntiles) ks = ntiles;
   if (ks < 1) ks = 1;
   if (deterministic_mode()) ks = 1;   // one writer per dW element: a fixed summation order

@@ -498,14 +498,12 @@ static hipError_t launch_wgrad_t(const WgradArgs& a0, int dtype, hipStream_t st)
   }
   size_t lds = wgrad_geom(a, dtype, th).lds;
   // bf16, 8-row tiles, 3x3: double-buffered tiles with the stores / loads as MFMA fillers (one barrier per tile)
-  static const bool no_pipe2 = getenv("OCTSEG_NO_WGRAD_PIPE2") != nullptr;
   bool std33 = NTAPS == 9 && a.istride == 1 && a.span_x == 3 && a.span_y == 3;
   for (int t = 0; std33 && t < 9; ++t) std33 = a.tap_dy[t] - a.min_dy == t / 3 && a.tap_dx[t] - a.min_dx == t % 3;
   // ... and the 2x2 taps of one ConvTranspose2d parity (wgrad_launches' order: both offsets descending) over dy's parity plane
-  static const bool no_pipe2_4 = getenv("OCTSEG_NO_WGRAD_PIPE2_4") != nullptr;   // A/B switch
-  bool std22 = NTAPS == 4 && !no_pipe2_4 && a.istride == 1 && a.span_x == 2 && a.span_y == 2;
+  bool std22 = NTAPS == 4 && a.istride == 1 && a.span_x == 2 && a.span_y == 2;
   for (int t = 0; std22 && t < 4; ++t) std22 = a.tap_dy[t] - a.min_dy == 1 - t / 2 && a.tap_dx[t] - a.min_dx == 1 - t % 2;
-  if (!no_pipe2 && pipelined && th == 8 && dtype != DT_F32 && (std33 || std22) && 2 * lds <= 150 * 1024) { pipelined = 2; lds *= 2; }
+  if (pipelined && th == 8 && dtype != DT_F32 && (std33 || std22) && 2 * lds <= 150 * 1024) { pipelined = 2; lds *= 2; }
   const int ntiles = a.N * ((a.OW + TW - 1) / TW) * ((a.OH + th - 1) / th);
   const int gx = (a.Cin + 63) / 64, gy = (a.Cout + 63) / 64;
   // One resident round at most (two workgroup slots per CU: 516 workgroups take twice as long as 504).  Every workgroup ends by
@@ -513,8 +511,7 @@ static hipError_t launch_wgrad_t(const WgradArgs& a0, int dtype, hipStream_t st)
   // bounds the encoder's 3x3 weight gradients (small maps, 256..512 channels) -- half the workgroups (one per CU, twice the
   // pixels each) halve it: encoder 3x3 wgrad 3.89 -> 2.98 ms per step, decoder 14.7 -> 14.4.  1x1 layers flush 16 KiB tiles and want
   // the occupancy: 512 there (256 measured 2.7 -> 3.7 ms).
-  static const int wg_env = getenv("OCTSEG_WGRAD_WGS") ? atoi(getenv("OCTSEG_WGRAD_WGS")) : 0;   // experiments
-  const int wg_target = wg_env > 0 ? wg_env : (NTAPS == 1 ? 512 : (a.wg_target > 0 ? a.wg_target : 256));
+  const int wg_target = NTAPS == 1 ? 512 : (a.wg_target > 0 ? a.wg_target : 256);
   int ks = wg_target / (gx * gy);
   if (ks > ntiles) ks = ntiles;
   if (ks < 1) ks = 1;

@@ -1,5 +1,6 @@
 #!/bin/bash
-# GPU box: A/B of environment switches inside ONE run (box-to-box spread is +-3 %).  usage: ab_perf.sh "<env A>" "<env B>" [more...]
+# GPU box: A/B of environment settings inside ONE run (box-to-box spread is +-3 %): two builds of the library (OCTSEG_LIB=path, see the
+# Makefile's B= / OUT= / EXTRA=) or one of the remaining switches.  usage: ab_perf.sh "<env A>" "<env B>" [more...]
 out=${OUT:-out}; mkdir -p $out
 i=0
 for e in "$@"; do

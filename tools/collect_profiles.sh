@@ -10,10 +10,8 @@ if [ "$part" != "workloads" ]; then
 python3 bench.py --full > $out/${tag}_bench_default.json 2> $out/${tag}_bench_default.err
 rocprofv3 --kernel-trace --stats -d $out/prof_${tag}_w -- python3 bench.py --full --steps 3 --warmup 2 --no-cpu-baseline > $out/prof_${tag}_w.log 2>&1
 python3 tools/prof_summary.py $(ls $out/prof_${tag}_w/*/*.db | head -1) $out/${tag}_w_bench_kernel_stats.csv 8 > $out/prof_${tag}_w.txt
-OCTSEG_NO_SIDE_STREAM=1 OCTSEG_NO_FWD_LANES=1 rocprofv3 --kernel-trace --stats -d $out/prof_${tag}_serial -- python3 bench.py --full --steps 3 --warmup 2 --no-cpu-baseline > $out/prof_${tag}_serial.log 2>&1
-python3 tools/prof_summary.py $(ls $out/prof_${tag}_serial/*/*.db | head -1) $out/${tag}_serial_kernel_stats.csv 8 > $out/prof_${tag}_serial.txt
 python3 tools/collect_traffic.py ${tag} > $out/${tag}_traffic.log 2>&1
-rm -rf $out/prof_${tag}_w $out/prof_${tag}_serial $out/pmc_${tag}_FETCH_SIZE $out/pmc_${tag}_WRITE_SIZE
+rm -rf $out/prof_${tag}_w $out/pmc_${tag}_FETCH_SIZE $out/pmc_${tag}_WRITE_SIZE
 OCTSEG_PROFILE_DUMP=$out/${tag}_layers_alone.csv python3 bench.py --full --steps 4 --warmup 2 --no-cpu-baseline > /dev/null 2>&1
 python3 tools/group_layers.py $out/${tag}_layers_alone.csv 2 > $out/${tag}_layer_groups.txt
 python3 bench.py --full --workload ensemble_704_fp16 --steps 30 > $out/${tag}_ensemble_b1.json 2> /dev/null
