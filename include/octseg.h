@@ -33,6 +33,8 @@
  *                                      write into mask[:, :, CLASS_ID - 1] (src/predict.py:92-100, data/utils.py:16-33)
  *   octseg_render_results              save_results: closing, ring, blur, two alpha pastes per class into the frame, the flat colour mask
  *                                      (src/data/utils.py:195-235, get_img_mask_union_pil src/models/smp/utils.py:203-213)
+ *   octseg_epoch_panels                log_predict_model_on_epoch, the per-epoch image | ground truth | prediction strips and the two W&B label
+ *                                      maps (src/models/smp/model.py:208-271, called from on_validation_epoch_end, model.py:134-148)
  *   octseg_stack_measure               the measurements of the app's get_analysis: set pixels per slice and class, and the ray walk of
  *                                      calculate_object_thickness per slice, class and degree (src/app/tools/analysis.py:60-130,189,199-200)
  *   octseg_plan_set_graph              (serving option, no reference counterpart) eval forwards of predict()
@@ -239,6 +241,28 @@ int octseg_debug_set_ingest_variant(int variant);
 int octseg_render_results(const float* stack, const uint8_t* frames, int N, int H, int W, int stack_channels, const int* class_channels,
                           const uint8_t* class_rgb, int C, const uint8_t* alpha_table, int ring_alpha, int close_iterations, uint8_t* overlay,
                           uint8_t* color_mask, void* stream);
+
+/* The per-epoch sample dump of the training loop: log_predict_model_on_epoch (reference src/models/smp/model.py:208-271, called from
+ * on_validation_epoch_end, model.py:134-148, when epoch % img_save_interval == 0) with the class colours / ids of src/data/utils.py:16-45, for a
+ * group of N frames that share a ground-truth source size, in ONE launch.
+ * frames: f32 [N][3][S][S], BGR planes of the frame already at input size, integer values 0..255 (what octseg_ingest_image writes: model.py:214-215);
+ * logits: f32 [N][C][S][S], the un-normalised forward of those frames (model.py:223-226, 192); gt: uint8 [N][src_h][src_w][src_channels], the RAW
+ * samples of the 4-channel TIFF at its own size (model.py:216); row_index [S] / col_index [S]: device int32 source index of every output row /
+ * column (resizeNN's rule, as for octseg_ingest_mask; required: model.py:217-221 is cv2.resize INTER_NEAREST); gt_channels: device int32 [C], the
+ * source channel of every class (CLASS_IDS[name] - 1; ids outside [0, src_channels) are clamped on the device, as in octseg_ingest_mask);
+ * class_rgb: device uint8 [C][3]; class_ids: device uint8 [C] (CLASS_IDS[name]).
+ * panels: uint8 [N][S][3 * S][3], RGB interleaved -- per row the frame with its planes reversed to RGB, then the ground-truth colour mask, then
+ * the prediction's: decoded as RGB this is what cv2.imwrite of the reference's BGR hstack (model.py:241-248) decodes to.  Both colour masks
+ * start (128, 128, 128); for class c = 0..C-1 IN ORDER (model.py:234-239) the ground truth takes class_rgb[c] where
+ * gt[n][row_index[y]][col_index[x]][gt_channels[c]] == 255 -- exactly 255, not != 0 -- and the prediction where sigmoid(logits[n][c][y][x]) > 0.5,
+ * the same fp32 sigmoid as octseg_mask_assemble and the Dice kernel; later classes overwrite earlier ones.
+ * labels: uint8 [N][2][S][S] or null (skipped): plane 0 the prediction, plane 1 the ground truth, class_ids[c] where the colour mask took
+ * class c's colour, 0 elsewhere (wandb_mask_inference / wandb_mask_ground_truth, model.py:232-239).
+ * Comparisons and integer moves only: the outputs EQUAL the reference's, no tolerance.  Outputs must not overlap inputs.  Enqueue only.
+ * Null pointer (but labels): OCTSEG_BAD_ARG; N, S, C, src_h, src_w or src_channels <= 0, or C > 16: OCTSEG_BAD_SHAPE. */
+int octseg_epoch_panels(const float* frames, const float* logits, const uint8_t* gt, int N, int S, int C, int src_h, int src_w, int src_channels,
+                        const int* row_index, const int* col_index, const int* gt_channels, const uint8_t* class_rgb, const uint8_t* class_ids,
+                        uint8_t* panels, uint8_t* labels, void* stream);
 
 /* The device part of the app's get_analysis (src/app/tools/analysis.py:133-250) for a pullback of N slices.  stack: f32 [N][H][W][stack_channels]
  * (what octseg_mask_assemble writes; any value != 0 counts as set, as in octseg_render_results).  counts: int32 [N][stack_channels], the number of

@@ -84,6 +84,8 @@ SYMBOLS = {
     'octseg_debug_set_ingest_variant': (C.c_int, [C.c_int]),
     # float32 mask stack + uint8 frames -> uint8 overlay + colour mask (csrc/render.hip)
     'octseg_render_results': (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P]),
+    # float32 frames + logits + raw uint8 ground truth -> uint8 image | ground truth | prediction strips and label maps (csrc/panels.hip)
+    'octseg_epoch_panels': (C.c_int, [_P, _P, _P] + [C.c_int] * 6 + [_P] * 8),
     # float32 mask stack + host ray table -> int32 set-pixel counts and per-degree radii (csrc/measure.hip)
     'octseg_stack_measure': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P]),
     'octseg_plan_set_loss': (C.c_int, [_P, C.c_int]),

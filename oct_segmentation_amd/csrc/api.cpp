@@ -268,6 +268,19 @@ int octseg_render_results(const float* stack, const uint8_t* frames, int N, int 
   return OCTSEG_OK;
 }
 
+// The per-epoch sample dump of the training loop (models/smp/model.py:208-271): see panels.hip.  Enqueue only.
+int octseg_epoch_panels(const float* frames, const float* logits, const uint8_t* gt, int N, int S, int C, int src_h, int src_w, int src_channels,
+                        const int* row_index, const int* col_index, const int* gt_channels, const uint8_t* class_rgb, const uint8_t* class_ids,
+                        uint8_t* panels, uint8_t* labels, void* stream) {
+  if (!frames || !logits || !gt || !row_index || !col_index || !gt_channels || !class_rgb || !class_ids || !panels)
+    return fail(OCTSEG_BAD_ARG, "null argument");
+  if (N <= 0 || S <= 0 || C <= 0 || C > 16 || src_h <= 0 || src_w <= 0 || src_channels <= 0)
+    return fail(OCTSEG_BAD_SHAPE, "epoch_panels: empty batch, frame or source, or not 1..16 classes");
+  HIPCHK(launch_epoch_panels(frames, logits, gt, N, S, C, src_h, src_w, src_channels, row_index, col_index, gt_channels, class_rgb, class_ids,
+                             panels, labels, (hipStream_t)stream));
+  return OCTSEG_OK;
+}
+
 // The measurements of the app's get_analysis (app/tools/analysis.py:60-130,189,199-200): see measure.hip.  Enqueue only.
 int octseg_stack_measure(const float* stack, int N, int H, int W, int stack_channels, const int* ray_pix, const int* ray_len, int R, int* counts,
                          int* radii, void* stream) {

@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <type_traits>
 #include "kernels.h"
+#include "sigmoid.h"
 
 namespace octseg {
 
@@ -840,11 +841,7 @@ hipError_t launch_stem_im2col(int dtype, const float* img, void* col, int N, int
 
 // ------------------------------------------------------------------ Dice loss
 static __device__ __forceinline__ float sigmoid_f(float z) { return 1.0f / (1.0f + __expf(-z)); }
-static __device__ __forceinline__ float sigmoid_acc(float z) {
-  // exp(logsigmoid(z)) as smp computes it, evaluated without cancellation
-  const float e = expf(-fabsf(z));
-  return z >= 0.f ? 1.0f / (1.0f + e) : e / (1.0f + e);
-}
+// sigmoid_acc: sigmoid.h (shared with panels.hip)
 template <typename V> static __device__ __forceinline__ V block_sum(V v, V* red) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;

@@ -309,6 +309,12 @@ hipError_t launch_render_results(const float* stack, const uint8_t* frames, int 
                                  const uint8_t* class_rgb, int C, const uint8_t* alpha_tab, int ring_alpha, int iters, uint8_t* overlay,
                                  uint8_t* cmask, hipStream_t st);
 
+// the per-epoch sample strips of the training loop (panels.hip): frame | ground truth | prediction as RGB bytes plus the two label maps, one launch
+// per group of frames that share a ground-truth source size; labels may be null
+hipError_t launch_epoch_panels(const float* frames, const float* logits, const uint8_t* gt, int N, int S, int C, int Hs, int Ws, int SC,
+                               const int* rows, const int* cols, const int* gt_ch, const uint8_t* class_rgb, const uint8_t* class_ids,
+                               uint8_t* panels, uint8_t* labels, hipStream_t st);
+
 // the app's per-pullback measurements (measure.hip): set pixels per slice and channel, and calculate_object_thickness's ray walk per slice,
 // channel and degree from the host's pixel table; clears counts, then two launches
 hipError_t launch_stack_measure(const float* stack, int N, int H, int W, int SC, const int* ray_pix, const int* ray_len, int R, int* counts,

@@ -3,11 +3,13 @@
 
 Same constructor keywords, same methods (``forward``, ``training_step``,
 ``validation_step``, ``configure_optimizers``, ``predict``,
-``load_from_checkpoint``), same ``state_dict`` keys (``model.*``, ``mean``,
-``std``).  Lightning, W&B, cv2 and the per-epoch image dump are not part of the
-hot path and are not reproduced (out of scope).
+``log_predict_model_on_epoch``, ``load_from_checkpoint``), same ``state_dict``
+keys (``model.*``, ``mean``, ``std``).  Lightning, W&B and cv2 are not part of
+the hot path and are not reproduced (out of scope).
 """
+import os
 import pickle
+from glob import glob
 
 import numpy as np
 import torch
@@ -19,6 +21,13 @@ from .metrics import DeferredMetrics, get_metrics_from_stats
 
 # reference src/data/utils.py:16-45
 CLASS_IDS = {'Lumen': 1, 'Fibrous cap': 2, 'Lipid core': 3, 'Vasa vasorum': 4}
+
+
+def vis_mask_path(img_path):
+    """The ground-truth TIFF the reference pairs with a ``vis/img`` file (model.py:216), with its string handling as written: EVERY ``img`` in
+    the path becomes ``mask`` -- the folder's, and one in a parent folder or in the file's stem too -- and the path is cut at its FIRST dot, a
+    dot in a folder name included.  Kept verbatim so that the same trees resolve to the same files."""
+    return f"{img_path.replace('img', 'mask').split('.')[0]}.tiff"
 
 
 class DiceLoss:
@@ -131,6 +140,8 @@ class OCTSegmentationModel(nn.Module):
         self.img_save_interval, self.save_wandb_media = img_save_interval, save_wandb_media
         self.fused_optimizer = fused_optimizer
         self.class_values = [CLASS_IDS[cl] for cl in self.classes if cl in CLASS_IDS]
+        self._vis_cache = None         # log_predict_model_on_epoch: the vis/ tree on the device, read once per run
+        self.last_vis_labels = {}      # save_wandb_media: stem -> uint8 [2, S, S] (prediction, ground truth) of the last dump
 
     # ---- model.py:65-71: (image - mean) / std is fused into the stem's im2col load
     def forward(self, image):
@@ -216,6 +227,92 @@ class OCTSegmentationModel(nn.Module):
     @staticmethod
     def to_tensor_shape(x):
         return x.transpose([2, 0, 1]).astype('float32')
+
+    # ---- model.py:208-271
+    def _vis_ingest(self):
+        """The ``<data_dir>/vis`` tree on the device, cached for the run under (data_dir, input_size): every file is read, uploaded and the
+        frames resized ONCE; the ground truth stays at source size (the panel kernel nearest-resizes it) in one tensor per source shape."""
+        from . import dataset, ingest
+        key = (self.data_dir, int(self.input_size))
+        if self._vis_cache is not None and self._vis_cache['key'] == key:
+            return self._vis_cache
+        S, dev = int(self.input_size), self.model.device
+        paths = sorted(glob(f'{self.data_dir}/vis/img/*.[pj][np][ge]*'))     # the reference's pattern; glob order is unspecified there
+        need = max([CLASS_IDS[cl] for cl in self.classes if cl in CLASS_IDS], default=1)
+        imgs, masks = [], []
+        for path in paths:
+            mask_path = vis_mask_path(path)
+            if not os.path.exists(mask_path):
+                raise FileNotFoundError(f'{path}: its ground truth {mask_path} does not exist')
+            mask = np.asarray(dataset.read_mask_tiff(mask_path))
+            if mask.ndim == 2:
+                mask = mask[:, :, None]
+            if mask.ndim != 3 or mask.shape[2] < need:
+                raise ValueError(f'{mask_path}: shape {mask.shape}, the classes {self.classes} need {need} channels')
+            if mask.dtype != np.uint8:     # only `== 255` of a sample is ever used (model.py:236,239): one byte per sample is enough
+                mask = ((mask == 255) * 255).astype(np.uint8)
+            imgs.append(dataset.read_image_bgr(path))
+            masks.append(np.ascontiguousarray(mask))
+        frames = torch.empty((len(paths), 3, S, S), dtype=torch.float32, device=dev)
+        for _, pos in dataset.group_by_shape([a.shape for a in imgs]):
+            out = ingest.resize_image_u8(torch.from_numpy(np.stack([imgs[p] for p in pos])).to(dev), S)
+            frames[torch.as_tensor(pos, device=dev)] = out
+        groups = [(pos, torch.from_numpy(np.stack([masks[p] for p in pos])).to(dev))
+                  for _, pos in dataset.group_by_shape([a.shape for a in masks])]
+        self._vis_cache = {'key': key, 'stems': [os.path.splitext(os.path.basename(p))[0] for p in paths], 'frames': frames, 'groups': groups}
+        return self._vis_cache
+
+    def log_predict_model_on_epoch(self, out_dir=None, epoch=None, batch_size=8):
+        """The per-epoch sample dump: for every ``<data_dir>/vis/img/*.[pj][np][ge]*`` with its ``vis/mask/<stem>.tiff``
+        (``vis_mask_path``) one strip image | ground truth | prediction at ``input_size``, written as
+        ``<out_dir>/<stem>_epoch_<epoch:03d>.png``; returns the written paths in sorted file order ([] at once when
+        ``<data_dir>/vis/img`` does not exist).  ``out_dir`` defaults to the reference's ``models/<model_name>/images_per_epoch``, ``epoch``
+        to ``self.epoch``.
+
+        The frames are predicted as they are resized -- no normalisation, sigmoid > 0.5 -- in chunks of ``batch_size`` and in
+        whatever mode the model is in (``fit()`` calls this from its validation branch: eval); the ground truth is painted where a class's
+        TIFF channel is exactly 255.  The reference's own call hands ``predict`` a CHW frame that ``predict`` transposes again and fails
+        on; this builds what it plainly means.  The files are read and uploaded once per run; a call is the forwards, one
+        ``octseg_epoch_panels`` launch per ground-truth source shape and ONE device-to-host copy of the strips.  PNG sources give the bytes
+        cv2 would; JPEG sources decode through Pillow, whose decoder may differ from cv2's in the last bit, so only PNG sources are exact
+        against the reference.  With ``save_wandb_media`` the two label maps (CLASS_IDS values; prediction, ground truth) are kept as
+        ``self.last_vis_labels[stem]``, uint8 [2, S, S] -- what the reference hands to ``wandb.Image``; W&B itself is out of scope."""
+        if not os.path.exists(f'{self.data_dir}/vis/img'):
+            return []
+        from PIL import Image
+        from . import postprocess
+        epoch = self.epoch if epoch is None else int(epoch)
+        out_dir = f'models/{self.model_name}/images_per_epoch' if out_dir is None else str(out_dir)
+        batch_size = int(batch_size)
+        if batch_size <= 0:
+            raise ValueError(f'batch_size must be positive, got {batch_size}')
+        vis = self._vis_ingest()
+        stems, frames = vis['stems'], vis['frames']
+        if not stems:
+            return []
+        n, S = len(stems), int(self.input_size)
+        want_labels = bool(self.save_wandb_media)
+        with torch.no_grad():
+            logits = torch.cat([self.predict_logits(frames[lo:lo + batch_size]) for lo in range(0, n, batch_size)])
+            panels = torch.empty((n, S, 3 * S, 3), dtype=torch.uint8, device=frames.device)
+            labels = torch.empty((n, 2, S, S), dtype=torch.uint8, device=frames.device) if want_labels else None
+            for pos, gt in vis['groups']:
+                idx = torch.as_tensor(pos, device=frames.device)
+                p, lab = postprocess.epoch_panels(frames[idx], logits[idx], gt, self.classes, labels=want_labels)
+                panels[idx] = p
+                if want_labels:
+                    labels[idx] = lab
+        host = panels.cpu().numpy()
+        os.makedirs(out_dir, exist_ok=True)
+        written = []
+        for i, stem in enumerate(stems):
+            path = os.path.join(out_dir, f'{stem}_epoch_{str(epoch).zfill(3)}.png')
+            Image.fromarray(host[i]).save(path)
+            written.append(path)
+        if want_labels:
+            lab_host = labels.cpu().numpy()
+            self.last_vis_labels = {stem: lab_host[i] for i, stem in enumerate(stems)}
+        return written
 
     # ---- checkpoint compatibility (predict.py:39-48): Lightning .ckpt = pickled dict with 'state_dict'
     def state_dict(self, *args, **kwargs):

@@ -114,6 +114,45 @@ def render_results(frames_u8, stack, classes, close_iterations=1):
     return overlay, color_mask
 
 
+def epoch_panels(frames_f32, logits, gt_u8, classes, labels=True):
+    """The array part of ``log_predict_model_on_epoch`` (reference ``src/models/smp/model.py:227-242``) for a group of frames whose ground
+    truth shares one source size: ``frames_f32`` float32 CUDA [N,3,S,S], BGR planes 0..255 (``ingest.resize_image_u8``); ``logits`` float32
+    CUDA [N,len(classes),S,S] (``predict_logits`` of those frames); ``gt_u8`` uint8 CUDA [N,Hs,Ws,channels], the RAW TIFF samples at their own
+    size -- the kernel nearest-resizes them with cv2's rule and paints a class where its channel is exactly 255.  ``classes`` in the order they
+    are drawn.  Returns ``(panels, labels)``: uint8 CUDA [N,S,3*S,3] RGB strips image | ground truth | prediction, and uint8 CUDA [N,2,S,S]
+    label maps (0: prediction, 1: ground truth; ``labels=False``: None).  One launch (``octseg_epoch_panels``, ``csrc/panels.hip``), no host
+    synchronisation."""
+    from .ingest import _nearest_dev
+    if not (torch.is_tensor(frames_f32) and frames_f32.is_cuda and frames_f32.dtype == torch.float32 and frames_f32.dim() == 4
+            and frames_f32.shape[1] == 3 and frames_f32.shape[2] == frames_f32.shape[3]):
+        raise ValueError('frames_f32 must be a float32 CUDA tensor [N, 3, S, S]')
+    if not (torch.is_tensor(logits) and logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 4):
+        raise ValueError('logits must be a float32 CUDA tensor [N, classes, S, S]')
+    if not (torch.is_tensor(gt_u8) and gt_u8.is_cuda and gt_u8.dtype == torch.uint8 and gt_u8.dim() == 4):
+        raise ValueError('gt_u8 must be a uint8 CUDA tensor [N, H, W, channels]')
+    if 0 in frames_f32.shape or 0 in logits.shape or 0 in gt_u8.shape:
+        raise ValueError('empty batch or frame')
+    classes = _check_classes(classes, gt_u8.shape[3])
+    n, _, s, _ = frames_f32.shape
+    if logits.device != frames_f32.device or gt_u8.device != frames_f32.device or tuple(logits.shape) != (n, len(classes), s, s) \
+            or gt_u8.shape[0] != n:
+        raise ValueError(f'frames {tuple(frames_f32.shape)}, logits {tuple(logits.shape)} and ground truth {tuple(gt_u8.shape)} must share '
+                         f'device and batch, and the logits the frame size and one plane per class')
+    dev = frames_f32.device
+    frames_f32, logits, gt_u8 = frames_f32.contiguous(), logits.contiguous(), gt_u8.contiguous()
+    _, sh, sw, sc = gt_u8.shape
+    key = tuple(classes)
+    ch = _const_dev(('render_ch', key), lambda: torch.tensor([CLASS_IDS[c] - 1 for c in classes], dtype=torch.int32), dev)
+    rgb = _const_dev(('render_rgb', key), lambda: torch.tensor([CLASS_COLORS_RGB[c] for c in classes], dtype=torch.uint8), dev)
+    ids = _const_dev(('panel_ids', key), lambda: torch.tensor([CLASS_IDS[c] for c in classes], dtype=torch.uint8), dev)
+    rows, cols = _nearest_dev(sh, s, dev), _nearest_dev(sw, s, dev)
+    panels = torch.empty((n, s, 3 * s, 3), dtype=torch.uint8, device=dev)
+    lab = torch.empty((n, 2, s, s), dtype=torch.uint8, device=dev) if labels else None
+    L.check(L.lib().octseg_epoch_panels(L.ptr(frames_f32), L.ptr(logits), L.ptr(gt_u8), n, s, len(classes), sh, sw, sc, L.ptr(rows), L.ptr(cols),
+                                        L.ptr(ch), L.ptr(rgb), L.ptr(ids), L.ptr(panels), L.ptr(lab), L.stream_ptr()))
+    return panels, lab
+
+
 def save_results(images, masks, images_name, classes, save_dir, close_iterations=1, device='cuda'):
     """utils.py:195-235.  ``images``: PIL images at output size.  They are converted to RGB: the reference pastes into whatever mode
     ``Image.open`` gave, and for other modes (L, RGBA, P) PIL's paste of an RGB colour behaves differently; RGB is what the demo frames are.

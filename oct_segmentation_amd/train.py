@@ -42,8 +42,16 @@ def fit(cfg, train_batches, val_batches=None, device='cuda', model_dir=None, aug
     """``cfg`` keys beyond train.yaml's: ``compute_dtype`` ('bf16' | 'fp32'), ``allreduce_slices``, ``encoder_weights`` (passed to
     the network factory: None = random init, a path / 'imagenet' = torchvision weights, see SegNet.load_encoder_weights) and
     ``defer_metrics`` (True: tp/fp/fn/tn and the loss of every step stay on the GPU and cross to the host ONCE per epoch instead
-    of once per step -- the per-step ``.cpu()`` of utils.py:25-35 is a device sync; the epoch rows are identical)."""
+    of once per step -- the per-step ``.cpu()`` of utils.py:25-35 is a device sync; the epoch rows are identical).
+
+    ``img_save_interval`` (train.yaml; None = off) with ``data_dir``: every epoch that is a multiple of it, after the epoch's validation rows
+    are written, rank 0 dumps the ``<data_dir>/vis`` samples as image | ground truth | prediction strips into
+    ``<model_dir>/images_per_epoch`` (``OCTSegmentationModel.log_predict_model_on_epoch``; model.py:134-148, train.py:66-67).  Needs
+    ``val_batches`` and ``model_dir``; without a ``vis/img`` folder nothing is written."""
     global _warned_random_init
+    interval = cfg.get('img_save_interval', 1)
+    if interval is not None and (isinstance(interval, bool) or not isinstance(interval, int) or interval <= 0):
+        raise ValueError(f'img_save_interval must be None or a positive int, got {interval!r}')
     world = int(os.environ.get('WORLD_SIZE', '1'))
     if world > 1:
         import torch.distributed as dist
@@ -62,7 +70,8 @@ def fit(cfg, train_batches, val_batches=None, device='cuda', model_dir=None, aug
     model = OCTSegmentationModel(cfg['architecture'], cfg['encoder'], f"{cfg['architecture']}_{cfg['encoder']}", 3,
                                  cfg['classes'], lr=cfg['lr'], weight_decay=cfg['weight_decay'],
                                  optimizer_name=cfg['optimizer'], input_size=cfg['input_size'], device=device, compute_dtype=dt,
-                                 encoder_weights=enc_w, defer_metrics=bool(cfg.get('defer_metrics', False)))
+                                 encoder_weights=enc_w, defer_metrics=bool(cfg.get('defer_metrics', False)), data_dir=cfg.get('data_dir'),
+                                 img_save_interval=interval, save_wandb_media=bool(cfg.get('save_wandb_media', False)))
     net = model.model
     exchange = None
     if world > 1:
@@ -76,7 +85,10 @@ def fit(cfg, train_batches, val_batches=None, device='cuda', model_dir=None, aug
     best_val = None   # ModelCheckpoint(monitor='val/loss', mode='min', save_top_k=1, filename='weights'), train.py:67-76
     if model_dir is not None and rank0:
         write_model_config(cfg, model_dir)   # the reference writes config.json before trainer.fit (train.py:105-119)
+        if interval is not None:
+            os.makedirs(os.path.join(model_dir, 'images_per_epoch'), exist_ok=True)   # train.py:66-67
     for epoch in range(1, int(cfg['epochs']) + 1):
+        model.epoch = epoch                  # the number metrics.csv carries: 1 for the first real epoch
         model.train()
         model.training_step_outputs.clear()
         n_train = 0
@@ -125,6 +137,9 @@ def fit(cfg, train_batches, val_batches=None, device='cuda', model_dir=None, aug
         if model_dir is not None and rank0:
             model.validation_best_metrics = write_epoch_rows(model_dir, cfg['classes'], epoch, train_outputs, val_outputs,
                                                              model.validation_best_metrics)
+            # model.py:144-145: behind the epoch's 'test' rows, the model still in the validation loop's eval mode
+            if val_batches is not None and interval is not None and epoch % interval == 0:
+                model.log_predict_model_on_epoch(out_dir=os.path.join(model_dir, 'images_per_epoch'), epoch=epoch)
         history.append(row)
     if model_dir is not None and rank0 and val_batches is None:   # nothing to monitor: keep the last epoch
         model.save_checkpoint(os.path.join(model_dir, 'weights.ckpt'), epoch=len(history))
