@@ -37,6 +37,9 @@
  *                                      maps (src/models/smp/model.py:208-271, called from on_validation_epoch_end, model.py:134-148)
  *   octseg_stack_measure               the measurements of the app's get_analysis: set pixels per slice and class, and the ray walk of
  *                                      calculate_object_thickness per slice, class and degree (src/app/tools/analysis.py:60-130,189,199-200)
+ *   octseg_plan_set_frozen_bn / octseg_plan_cam_target / octseg_net_backward_seeded / octseg_cam_maps
+ *                                      CAMProcessor.extract_activation_map / overlay_activation_map over pytorch-grad-cam on model.eval()
+ *                                      (src/models/cam_processor.py:83-98, src/models/visualize_activation_maps.py:102-199)
  *   octseg_plan_set_graph              (serving option, no reference counterpart) eval forwards of predict()
  *                                      (model.py:183-200) replayed as one hipGraph
  *   octseg_plan_params_changed         optimizer.step() / load_state_dict() side effect: weight images are stale
@@ -281,6 +284,44 @@ int octseg_epoch_panels(const float* frames, const float* logits, const uint8_t*
  * H * W >= 2^31: OCTSEG_BAD_SHAPE. */
 int octseg_stack_measure(const float* stack, int N, int H, int W, int stack_channels, const int* ray_pix, const int* ray_len, int R, int* counts,
                          int* radii, void* stream);
+
+/* Class activation maps (reference src/models/cam_processor.py:83-98 and src/models/visualize_activation_maps.py:102-199 over the
+ * pytorch-grad-cam package; restated in DESIGN.md section 5e, parity with the package itself is not pinned).
+ *
+ * octseg_plan_set_frozen_bn(plan, 1): the reference explains a model in eval().  Training-path forwards of the plan (octseg_net_forward with
+ * train = 1) then keep activations and ReLU masks as in training but read every BatchNorm from its running statistics: no buffer is written, a
+ * batch of one value per channel is accepted.  Built for unet | unetplusplus | linknet | manet over the ResNets in f32 / bf16; every other
+ * pair returns OCTSEG_UNSUPPORTED_ARCH (f16: OCTSEG_BAD_DTYPE) and octseg_last_error() says why.  Use a plan of its own for this.
+ * octseg_plan_cam_target: workspace byte offsets of the output of encoder.layer4's last block (the reference's target layer, after the residual
+ * add and the ReLU) and of its gradient, NHWC in the plan dtype; dims = {N, h, w, K}.
+ * octseg_net_backward_seeded: backward of such a forward from dL/dlogits (device NCHW f32 [batch][classes][H][W], e.g. a mask on one class
+ * plane: the reference's SemanticSegmentationTarget) down to the target tensor's gradient.  Data gradients only: no weight, bias or BatchNorm
+ * parameter gradient is launched, no gradient arena is read or written.
+ *
+ * octseg_cam_maps: A, G device NHWC [N][h][w][K] of `dtype` (f32 | bf16; K a multiple of 8) -> maps f32 [N][S][S].  method: 0 GradCAM,
+ * 1 HiResCAM, 2 GradCAMElementWise, 3 GradCAMPlusPlus, 4 XGradCAM, 5 LayerCAM.  Per frame: the method's raw map, max(., 0), (x - min) / (1e-7 +
+ * max), cv2.resize(INTER_LINEAR) to S x S in float32, max(., 0), the same scaling again.  scratch: octseg_cam_scratch_bytes(N, h, w, K) device bytes.
+ * Optional outputs (null = skipped), all enqueued behind the maps on the same stream:
+ *   bin      uint8 [N][S][S] = (map > threshold) * 255;
+ *   counts   int32 [N][3] = tp, pred, true of (map > threshold) read through row_index [gt_h] / col_index [gt_w] (device int32, the source index
+ *            of every ground-truth row / column: cv2's INTER_NEAREST rule, as for octseg_ingest_mask; clamped on the device) against
+ *            gt uint8 [N][gt_h][gt_w], any value != 0 counting as set;
+ *   overlay  uint8 [N][S][S][3] BGR = show_cam_on_image(frame / 255, map, use_rgb=False, image_weight): frames f32 [N][3][S][S] BGR planes
+ *            0..255, jet_bgr device uint8 [256][3] the colour table in BGR (the host mirror builds it, oct_segmentation_amd/cam.py),
+ *            o = (1 - image_weight) * jet[uint8(255 * map)] / 255 + image_weight * frame / 255, divided by its maximum over the frame,
+ *            times 255, truncated.
+ * Enqueue only.  Null A / G / scratch / maps or a requested output without its inputs: OCTSEG_BAD_ARG; bad extents: OCTSEG_BAD_SHAPE. */
+int octseg_plan_set_frozen_bn(octseg_plan* plan, int on);
+int octseg_plan_cam_target(const octseg_plan* plan, size_t* act_off, size_t* grad_off, int* dims);
+int octseg_net_backward_seeded(octseg_plan* plan, const float* params, void* workspace, const float* dlogits, void* stream);
+size_t octseg_cam_scratch_bytes(int N, int h, int w, int K);
+int octseg_cam_maps(int dtype, const void* A, const void* G, int N, int h, int w, int K, int method, int S, void* scratch, float* maps,
+                    float threshold, uint8_t* bin, const uint8_t* gt, int gt_h, int gt_w, const int* row_index, const int* col_index, int* counts,
+                    const float* frames, const uint8_t* jet_bgr, double image_weight, uint8_t* overlay, void* stream);
+
+/* octseg_cam_overlay: the overlay of octseg_cam_maps for maps that exist already (f32 [N][S][S], used as they are); scratch: 16 * N device bytes. */
+int octseg_cam_overlay(const float* maps, const float* frames, const uint8_t* jet_bgr, int N, int S, double image_weight, uint8_t* overlay,
+                       void* scratch, void* stream);
 
 /* Criterion evaluated by octseg_dice_forward / octseg_net_train_step and differentiated by the backward entry points.
  * OCTSEG_LOSS_DICE (default) = smp.losses.DiceLoss(MULTILABEL_MODE, from_logits=True), the reference's (model.py:55);

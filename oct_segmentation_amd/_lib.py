@@ -88,6 +88,13 @@ SYMBOLS = {
     'octseg_epoch_panels': (C.c_int, [_P, _P, _P] + [C.c_int] * 6 + [_P] * 8),
     # float32 mask stack + host ray table -> int32 set-pixel counts and per-degree radii (csrc/measure.hip)
     'octseg_stack_measure': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P]),
+    # class activation maps: frozen-BatchNorm forward, seeded data-only backward, the map kernels (csrc/cam.hip)
+    'octseg_plan_set_frozen_bn': (C.c_int, [_P, C.c_int]),
+    'octseg_plan_cam_target': (C.c_int, [_P, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
+    'octseg_net_backward_seeded': (C.c_int, [_P, _P, _P, _P, _P]),
+    'octseg_cam_scratch_bytes': (C.c_size_t, [C.c_int] * 4),
+    'octseg_cam_maps': (C.c_int, [C.c_int, _P, _P] + [C.c_int] * 6 + [_P, _P, C.c_float, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_double, _P, _P]),
+    'octseg_cam_overlay': (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_double, _P, _P, _P]),
     'octseg_plan_set_loss': (C.c_int, [_P, C.c_int]),
     'octseg_dice_forward': (C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
     'octseg_net_backward': (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_float, _P]),

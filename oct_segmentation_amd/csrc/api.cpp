@@ -293,6 +293,96 @@ int octseg_stack_measure(const float* stack, int N, int H, int W, int stack_chan
   return OCTSEG_OK;
 }
 
+// ---------------------------------------------------------------- class activation maps (cam.hip)
+// Which graphs the frozen-BatchNorm mode and the seeded backward are built for, and why not the others.
+static int cam_supported(const octseg_plan* p) {
+  const std::string& a = p->arch;
+  if (p->dtype == OCTSEG_F16) return fail(OCTSEG_BAD_DTYPE, "f16 is a serving dtype: it has no backward, so no class activation maps");
+  if (p->encoder.compare(0, 6, "resnet") != 0)
+    return fail(OCTSEG_UNSUPPORTED_ARCH, "encoder '" + p->encoder + "' has no encoder.layer4 (the reference's target layer does not exist there either)");
+  if (a == "pan" || a == "deeplabv3" || a == "deeplabv3plus")
+    return fail(OCTSEG_UNSUPPORTED_ARCH, "arch '" + a + "': encoder.layer4 runs dilated, in a parity-re-arranged layout; its block output is not the reference's tensor" +
+                                         (a == "pan" ? "" : ", and the graph holds a dropout op"));
+  if (a == "fpn" || a == "pspnet")
+    return fail(OCTSEG_UNSUPPORTED_ARCH, "arch '" + a + "': the graph holds a dropout op, which the frozen mode does not switch off" +
+                                         (a == "pspnet" ? "; PSPNet never runs encoder.layer4" : ""));
+  if (a != "unet" && a != "unetplusplus" && a != "linknet" && a != "manet")
+    return fail(OCTSEG_UNSUPPORTED_ARCH, "arch '" + a + "' has no class-activation-map path");
+  if (cam_target_op(p) < 0) return fail(OCTSEG_UNSUPPORTED_ARCH, "internal: no block output of encoder.layer4 in this graph");
+  return OCTSEG_OK;
+}
+
+// Frozen-BatchNorm mode (the reference runs Grad-CAM on model.eval(), visualize_activation_maps.py:102): octseg_net_forward(train = 1) keeps the
+// training op path -- unfolded weight images, saved activations and ReLU masks -- with every BatchNorm on its running statistics; no buffer is
+// written.  The backward of such a forward is octseg_net_backward_seeded.
+int octseg_plan_set_frozen_bn(octseg_plan* p, int on) {
+  if (!p) return fail(OCTSEG_BAD_ARG, "null argument");
+  if (on) { const int rc = cam_supported(p); if (rc) return rc; }
+  p->frozen_bn = on != 0;
+  return OCTSEG_OK;
+}
+
+// Workspace byte offsets of the OUTPUT of encoder.layer4's last block (after the residual add and the ReLU: the reference's target layer
+// model.model.encoder.layer4[-1]) and of its gradient; dims = {N, h, w, K}.  NHWC, plan dtype.
+int octseg_plan_cam_target(const octseg_plan* p, size_t* act_off, size_t* grad_off, int* dims) {
+  if (!p) return fail(OCTSEG_BAD_ARG, "null argument");
+  const int rc = cam_supported(p);
+  if (rc) return rc;
+  const TensorInfo& t = p->tensors[p->ops[cam_target_op(p)].out];
+  if (act_off) *act_off = t.off;
+  if (grad_off) *grad_off = t.goff;
+  if (dims) { dims[0] = t.N; dims[1] = t.H; dims[2] = t.W; dims[3] = t.C; }
+  return OCTSEG_OK;
+}
+
+// Backward of a frozen-mode forward from a caller-made dL/dlogits (NCHW f32 [B][classes][H][W]) down to the gradient of the CAM target
+// tensor: data gradients and frozen-BatchNorm sweeps only -- no weight-, bias- or BatchNorm-parameter gradient is launched and no gradient
+// arena is touched; the walk over the op list ends in front of the target's producer.
+int octseg_net_backward_seeded(octseg_plan* p, const float* params, void* workspace, const float* dlogits, void* stream) {
+  if (!p || !params || !workspace || !dlogits) return fail(OCTSEG_BAD_ARG, "null argument");
+  if (!p->frozen_bn) return fail(OCTSEG_BAD_ARG, "octseg_net_backward_seeded needs a plan in frozen-BatchNorm mode (octseg_plan_set_frozen_bn)");
+  Exec E{p, params, nullptr, nullptr, (char*)workspace, (hipStream_t)stream, 1};
+  E.seed = dlogits; E.data_only = true; E.stop_op = cam_target_op(p);
+  return run_backward(E, nullptr, nullptr, 1.f);
+}
+
+size_t octseg_cam_scratch_bytes(int N, int h, int w, int K) {
+  if (N <= 0 || h <= 0 || w <= 0 || K <= 0) return 0;
+  return cam_scratch_bytes(N, h, w, K);
+}
+
+int octseg_cam_maps(int dtype, const void* A, const void* G, int N, int h, int w, int K, int method, int S, void* scratch, float* maps,
+                    float threshold, uint8_t* bin, const uint8_t* gt, int gt_h, int gt_w, const int* row_index, const int* col_index, int* counts,
+                    const float* frames, const uint8_t* jet_bgr, double image_weight, uint8_t* overlay, void* stream) {
+  if (!A || !G || !scratch || !maps) return fail(OCTSEG_BAD_ARG, "null argument");
+  if (dtype != OCTSEG_F32 && dtype != OCTSEG_BF16) return fail(OCTSEG_BAD_DTYPE, "cam_maps: A and G are f32 or bf16 (f16 plans have no backward)");
+  if (method < 0 || method > 5) return fail(OCTSEG_BAD_ARG, "cam_maps: method must be 0 GradCAM, 1 HiResCAM, 2 GradCAMElementWise, 3 GradCAMPlusPlus, 4 XGradCAM, 5 LayerCAM");
+  if (N <= 0 || h <= 0 || w <= 0 || K <= 0 || K % 8 != 0 || S <= 0 || S > 16384 || (long long)h * w > (1ll << 24) || (long long)N * h * w >= (1ll << 31) ||
+      (long long)N * K >= (1ll << 31))
+    return fail(OCTSEG_BAD_SHAPE, "cam_maps: empty batch or map, K not a multiple of 8, or S outside 1..16384");
+  if (counts && (!gt || !row_index || !col_index)) return fail(OCTSEG_BAD_ARG, "cam_maps: counts need the ground-truth plane and both index tables");
+  if (counts && (gt_h <= 0 || gt_w <= 0 || (long long)gt_h * gt_w >= (1ll << 31))) return fail(OCTSEG_BAD_SHAPE, "cam_maps: empty or oversized ground truth");
+  if (overlay && (!frames || !jet_bgr)) return fail(OCTSEG_BAD_ARG, "cam_maps: the overlay needs the frames and the colour table");
+  if (overlay && !(image_weight >= 0.0 && image_weight <= 1.0)) return fail(OCTSEG_BAD_ARG, "cam_maps: image_weight must be in [0, 1]");
+  CamArgs c;
+  memset(&c, 0, sizeof(c));
+  c.A = A; c.G = G; c.N = N; c.h = h; c.w = w; c.K = K; c.method = method; c.S = S; c.scratch = scratch; c.maps = maps;
+  c.threshold = threshold; c.bin = bin; c.gt = gt; c.gt_h = gt_h; c.gt_w = gt_w; c.row_index = row_index; c.col_index = col_index; c.counts = counts;
+  c.frames = frames; c.jet = jet_bgr; c.image_weight = image_weight; c.overlay = overlay;
+  HIPCHK(launch_cam_maps(dtype, c, (hipStream_t)stream));
+  return OCTSEG_OK;
+}
+
+// The overlay alone, of maps that exist already (CAMProcessor.overlay_activation_map): show_cam_on_image as in octseg_cam_maps, no rescaling.
+int octseg_cam_overlay(const float* maps, const float* frames, const uint8_t* jet_bgr, int N, int S, double image_weight, uint8_t* overlay,
+                       void* scratch, void* stream) {
+  if (!maps || !frames || !jet_bgr || !overlay || !scratch) return fail(OCTSEG_BAD_ARG, "null argument");
+  if (N <= 0 || S <= 0 || S > 16384) return fail(OCTSEG_BAD_SHAPE, "cam_overlay: empty batch, or S outside 1..16384");
+  if (!(image_weight >= 0.0 && image_weight <= 1.0)) return fail(OCTSEG_BAD_ARG, "cam_overlay: image_weight must be in [0, 1]");
+  HIPCHK(launch_cam_overlay(maps, frames, jet_bgr, N, S, image_weight, overlay, scratch, (hipStream_t)stream));
+  return OCTSEG_OK;
+}
+
 int octseg_dice_forward(octseg_plan* p, void* workspace, const float* logits, const float* target, float* loss,
                         long long* stats, void* stream) {
   if (!p || !workspace || !logits || !target || !loss) return fail(OCTSEG_BAD_ARG, "null argument");
@@ -486,6 +576,16 @@ int octseg_conv2d_backward_weight(int dtype, const void* x, const void* dy, floa
 }  // extern "C"
 
 bool octseg::detail::serial_mode() { return g_serial; }
+
+int octseg::detail::cam_target_op(const octseg_plan* P) {
+  int found = -1;
+  for (int oi = 0; oi < (int)P->ops.size(); ++oi) {
+    const Op& op = P->ops[oi];
+    if (op.kind != OP_BN_ACT || op.y.bn < 0 || op.res.t < 0 || op.out < 0) continue;   // a residual block's output: relu(bn(y) + shortcut)
+    if (P->bns[op.y.bn].name.compare(0, 15, "encoder.layer4.") == 0 && P->tensors[op.out].need_grad) found = oi;
+  }
+  return found;
+}
 
 static int g_deterministic = -1;   // -1: not decided yet (environment)
 bool octseg::deterministic_mode() {

@@ -378,6 +378,7 @@ hipError_t launch_sefc_bwd(int dtype, const SefcArgs& a, hipStream_t st) {
   if (lds > 60 * 1024 || a.R < 1) return hipErrorInvalidValue;
   if (dtype == DT_F32) hipLaunchKernelGGL(sefc_bwd_kernel<float>, dim3(a.N), dim3(256), lds, st, a);
   else hipLaunchKernelGGL(sefc_bwd_kernel<bf16_t>, dim3(a.N), dim3(256), lds, st, a);
+  if (a.dw1 == nullptr) return hipGetLastError();   // data-only backward: no parameter gradient wanted
   const int total = 2 * a.C * a.R + a.C + a.R;
   if (dtype == DT_F32) hipLaunchKernelGGL(sefc_wgrad_kernel<float>, dim3(grid_for((size_t)total, 256)), dim3(256), 0, st, a);
   else hipLaunchKernelGGL(sefc_wgrad_kernel<bf16_t>, dim3(grid_for((size_t)total, 256)), dim3(256), 0, st, a);

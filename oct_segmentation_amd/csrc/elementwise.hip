@@ -242,6 +242,30 @@ hipError_t launch_bn_finalize_eval(int C, const float* gamma, const float* beta,
   return hipGetLastError();
 }
 
+// Frozen BatchNorm inside the training op path (class activation maps: the model is in eval(), the activations and ReLU masks are kept):
+// the four vectors the forward's consumers and the backward's apply sweep read come from the running buffers, and the apply sweep's two
+// batch coefficients are zero, which leaves dy = gamma * rstd * mask * g.  The buffers are read only.
+__global__ void bn_finalize_frozen_kernel(int C, const float* gamma, const float* beta, const float* rm, const float* rv, float eps,
+                                          float* scale, float* shift, float* mean, float* rstd, float* coef) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c < C) {
+    const float sd = sqrtf(rv[c] + eps);
+    const float sc = gamma[c] / sd;
+    scale[c] = sc;
+    shift[c] = beta[c] - rm[c] * sc;
+    mean[c] = rm[c];
+    rstd[c] = 1.0f / sd;
+    coef[2 * c] = 0.f;
+    coef[2 * c + 1] = 0.f;
+  }
+}
+hipError_t launch_bn_finalize_frozen(int C, const float* gamma, const float* beta, const float* running_mean, const float* running_var, float eps,
+                                     float* scale, float* shift, float* mean, float* rstd, float* coef, hipStream_t st) {
+  hipLaunchKernelGGL(bn_finalize_frozen_kernel, dim3((C + 255) / 256), dim3(256), 0, st, C, gamma, beta, running_mean, running_var, eps, scale,
+                     shift, mean, rstd, coef);
+  return hipGetLastError();
+}
+
 // ------------------------------------------------------------------ BN apply (+residual, +relu, +skip)
 template <typename T>
 __global__ __launch_bounds__(256) void bn_act_kernel(const BnActArgs a) {

@@ -151,6 +151,11 @@ hipError_t launch_bn_finalize_eval(int C, const float* gamma, const float* beta,
                                    const float* running_var, float eps, float* scale, float* shift,
                                    hipStream_t st);
 
+// frozen (training op path on the running statistics): scale = gamma / sqrt(rv + eps), shift = beta - rm * scale, mean = rm, rstd = 1 / sqrt(rv + eps),
+// and the backward's two coefficients coef[C][2] = 0 -- bn_bwd_apply then computes gamma * rstd * mask * g.  Writes no buffer.
+hipError_t launch_bn_finalize_frozen(int C, const float* gamma, const float* beta, const float* running_mean, const float* running_var, float eps,
+                                     float* scale, float* shift, float* mean, float* rstd, float* coef, hipStream_t st);
+
 // eval: scale/shift of every BatchNorm of a plan in one launch (job table + channel prefix sums in the workspace)
 struct BnEvalJob { size_t gamma_off, beta_off, rm_off, rv_off /*floats*/, ss_off /*bytes*/; int C;
                    size_t bias_off; /* floats: bias of the conv in front of this BN, folded into the shift (~0: none) */
@@ -319,6 +324,22 @@ hipError_t launch_epoch_panels(const float* frames, const float* logits, const u
 // channel and degree from the host's pixel table; clears counts, then two launches
 hipError_t launch_stack_measure(const float* stack, int N, int H, int W, int SC, const int* ray_pix, const int* ray_len, int R, int* counts,
                                 int* radii, hipStream_t st);
+
+// class activation maps (cam.hip).  launch_cam_seed: dL/dlogits NCHW f32 [B][C][HW] -> NHWC T rows padded to CP channels (launch_dice_bwd's layout).
+hipError_t launch_cam_seed(int dtype, const float* seed, void* dlogits, int B, int C, size_t HW, int CP, hipStream_t st);
+// launch_cam_maps: A, G NHWC T [N][h][w][K] -> maps f32 [N][S][S] in [0, 1] and, where the pointers are set, the thresholded map, the confusion
+// counts against a ground-truth plane and the JET overlay (see include/octseg.h, octseg_cam_maps).  scratch: cam_scratch_bytes() device bytes.
+struct CamArgs {
+  const void* A; const void* G; int N, h, w, K, method, S;
+  void* scratch; float* maps;
+  float threshold; uint8_t* bin;
+  const uint8_t* gt; int gt_h, gt_w; const int* row_index; const int* col_index; int* counts;
+  const float* frames; const uint8_t* jet; double image_weight; uint8_t* overlay;
+};
+size_t cam_scratch_bytes(int N, int h, int w, int K);
+hipError_t launch_cam_maps(int dtype, const CamArgs& a, hipStream_t st);
+hipError_t launch_cam_overlay(const float* maps, const float* frames, const uint8_t* jet, int N, int S, double image_weight, uint8_t* overlay,
+                              void* acc /* 16 N device bytes */, hipStream_t st);
 
 // fused optimizers over the flat fp32 arenas
 struct OptArgs {

@@ -165,6 +165,8 @@ struct octseg_plan {
   struct { int w[6], b[6], bn[6]; int pool = -1; size_t scratch_off = 0, gscratch_off = 0; } fpa;   // PAN's FPA pyramid: parameter / BatchNorm indices of its six
                                                                                                      // one-channel layers, the pooled-input tensor, f32 scratch
   size_t dlogits_off = 0;                    // NHWC padded dL/dlogits
+  bool frozen_bn = false;                    // octseg_plan_set_frozen_bn: training-path forwards and backwards with BatchNorm on its running statistics
+                                             // (scale / shift / mean / rstd from the buffers, nothing written back; backward = gamma * rstd * mask * g)
   int loss_kind = 0;                         // LOSS_DICE | LOSS_BCE | LOSS_DICE_BCE (octseg_plan_set_loss)
   size_t dice_off = 0;                       // double sums[1 + B][C][DICE_NS]: totals, then one replica per image
   int col_tensor = -1;

@@ -34,14 +34,19 @@ static int bn_backward(Exec& E, int bn, const void* g, int mask, const void* out
   // --batch 2, +-0 at 4, -2 % at 16; 64 rows -9 % at 2; a size rule (256 rows up to 4 M elements) moved nothing: 1024 stays.
   if (rows > 1024) rows = 1024;
   a.rows = (int)rows;
-  a.dgamma = E.grads + P->params[b.gamma].off;
-  a.dbeta = E.grads + P->params[b.beta].off;
+  if (E.grads) {
+    a.dgamma = E.grads + P->params[b.gamma].off;
+    a.dbeta = E.grads + P->params[b.beta].off;
+  }
   a.coef = E.bn_coef(bn);
   a.dy = E.grad(b.y);
   a.res_grad = res_grad; a.res_store = res_store;
   E.ginit[b.y] = 1;   // written (stored) by the apply pass below
   const double tbytes = (double)a.npix * b.C * dtype_size(P->dtype);   // class 3 = HBM-bound sweeps: "flops" carries algorithmic bytes
-  if (a.npix <= (size_t)BN_SMALL_COUNT) {   // small tensors: reduce, finalize and apply in one launch, in double (elementwise.hip)
+  if (P->frozen_bn) {
+    // running statistics: no batch term in the gradient.  The forward's finalize left coef = 0 (launch_bn_finalize_frozen), so the apply sweep
+    // alone computes dy = gamma * rstd * mask * g -- small tensors included; no dgamma / dbeta
+  } else if (a.npix <= (size_t)BN_SMALL_COUNT) {   // small tensors: reduce, finalize and apply in one launch, in double (elementwise.hip)
     ProfScope ps(3, tbytes * ((mask == 2 && !maskbits) ? 5 : 4), E.st, b.name + ".bwd_small");
     HIPCHK(launch_bn_bwd_small(P->dtype, a, E.st));
     return OCTSEG_OK;
@@ -63,6 +68,7 @@ static int conv_backward(Exec& E, const ConvLayer& L, const void* dy, int dyC) {
   octseg_plan* P = E.P;
   const size_t esz = dtype_size(P->dtype);
   const Geom g = E.geom(L);
+  if (E.data_only && L.stem) return OCTSEG_OK;   // the frame needs no gradient
   if (L.stem && (P->stem_k == 7 && thin_stem_eligible(P->dtype))) {
     // the forward built no im2col tensor.  Weight gradient straight from the frame (thin.hip); the deterministic-reduction mode keeps the
     // atomics-free kernel and rebuilds the im2col rows for it here.  The frame needs no gradient.
@@ -286,7 +292,7 @@ static int conv_backward(Exec& E, const ConvLayer& L, const void* dy, int dyC) {
     }
     return OCTSEG_OK;
   };
-  { const int rc = wgrad_part(); if (rc) return rc; }
+  if (!E.data_only) { const int rc = wgrad_part(); if (rc) return rc; }
   return dgrad_part();
 }
 
@@ -352,10 +358,19 @@ int run_backward(Exec& E, const float* logits, const float* target, float grad_s
     S->cb(S->user, k, S->bounds[k], S->bounds[k + 1]);
     return OCTSEG_OK;
   };
-  HIPCHK(hipMemsetAsync(E.grads, 0, P->param_numel * sizeof(float), E.st));
+  if (E.data_only) {
+    if (S || !P->frozen_bn) return fail(OCTSEG_BAD_ARG, "a data-only backward needs the plan in frozen-BatchNorm mode and takes no slices");
+    for (int oi = (int)P->ops.size() - 1; oi > E.stop_op; --oi) {   // every op of the walk must have a gradient that leaves the parameters alone
+      const OpKind k = P->ops[oi].kind;
+      if (k == OP_GN || k == OP_DW || k == OP_DWG || k == OP_BNX || k == OP_FPA || k == OP_MERGE || k == OP_DROPE || k == OP_DROP2D)
+        return fail(OCTSEG_UNSUPPORTED_ARCH, "a data-only backward of this graph is not built (" + P->arch + ")");
+    }
+  } else {
+    HIPCHK(hipMemsetAsync(E.grads, 0, P->param_numel * sizeof(float), E.st));
+  }
   HIPCHK(hipMemsetAsync(E.ws + P->fin_cnt_off, 0, 2 * 64 * sizeof(unsigned), E.st));
   E.ginit.assign(P->tensors.size(), 0);
-  if (!serial_mode()) {
+  if (!serial_mode() && !E.data_only) {
     // (a step that is being captured / replayed as one hipGraph keeps the default priority: replaying a graph whose side branch was captured
     //  from a lowest-priority stream took 34.9 instead of 20.7 ms per step at 2 frames, profiles/r4_graph_ab.txt)
     hipStream_t* wsp = P->tgraph_enabled ? &P->side : &P->side_bwd;
@@ -370,10 +385,15 @@ int run_backward(Exec& E, const float* logits, const float* target, float grad_s
     HIPCHK(hipStreamWaitEvent(E.wst, P->ev_fork, 0));
   }
   // dL/dlogits (NHWC, padded channels)
-  const DiceArgs da = dice_args(P, E.ws, logits, target);
-  HIPCHK(launch_dice_bwd(P->dtype, da, grad_scale, E.ws + P->dlogits_off, P->dlogits_C, E.st));
+  if (E.seed) {
+    HIPCHK(launch_cam_seed(P->dtype, E.seed, E.ws + P->dlogits_off, P->B, P->classes, (size_t)P->H * P->W, P->dlogits_C, E.st));
+  } else {
+    const DiceArgs da = dice_args(P, E.ws, logits, target);
+    HIPCHK(launch_dice_bwd(P->dtype, da, grad_scale, E.ws + P->dlogits_off, P->dlogits_C, E.st));
+  }
   int rc;
   for (int oi = (int)P->ops.size() - 1; oi >= 0; --oi) {
+    if (oi == E.stop_op) break;   // every consumer of that op's output has run: its gradient is complete
     const Op& op = P->ops[oi];
     switch (op.kind) {
       case OP_STEM_COL: break;
@@ -483,8 +503,10 @@ int run_backward(Exec& E, const float* logits, const float* target, float grad_s
         memset(&a, 0, sizeof(a));
         a.m = E.act(op.in); a.ds = E.grad(op.out); a.dm = E.grad(op.in);
         a.w1 = E.params + P->params[op.ins[0]].off; a.w2 = E.params + P->params[op.ins[2]].off;
-        a.dw1 = E.grads + P->params[op.ins[0]].off; a.db1 = E.grads + P->params[op.ins[1]].off;
-        a.dw2 = E.grads + P->params[op.ins[2]].off; a.db2 = E.grads + P->params[op.ins[3]].off;
+        if (E.grads) {   // (a data-only backward leaves them null: launch_sefc_bwd then skips its weight-gradient launch)
+          a.dw1 = E.grads + P->params[op.ins[0]].off; a.db1 = E.grads + P->params[op.ins[1]].off;
+          a.dw2 = E.grads + P->params[op.ins[2]].off; a.db2 = E.grads + P->params[op.ins[3]].off;
+        }
         a.h = (float*)(E.ws + op.aux_off); a.dh = a.h + (size_t)t.N * op.up;
         a.N = t.N; a.C = t.C; a.R = op.up; a.act = op.oc0;
         HIPCHK(launch_sefc_bwd(P->dtype, a, E.st));

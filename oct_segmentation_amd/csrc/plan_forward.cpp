@@ -105,7 +105,8 @@ static int tied_forward(Exec& E, const ConvLayer& L, hipStream_t st, float* slab
 int run_forward(Exec& E, const float* image, float* logits, int normalize, const float* mean, const float* stdv) {
   octseg_plan* P = E.P;
   if (!P->run_error.empty()) return fail(OCTSEG_BAD_SHAPE, P->run_error);
-  if (E.train)
+  const bool frozen = E.train && P->frozen_bn;   // BatchNorm on its running statistics inside the training op path (octseg_plan_set_frozen_bn)
+  if (E.train && !frozen)
     for (auto& b : P->bns)
       if (b.count <= 1.0) {   // torch.nn.functional.batch_norm raises the same way (reference runs it in training)
         const TensorInfo& t = P->tensors[b.y];
@@ -247,7 +248,10 @@ int run_forward(Exec& E, const float* image, float* logits, int normalize, const
         const float* beta = E.params + P->params[b.beta].off;
         rc = need(lane, tseq[b.y]);   // same lane as its conv by construction; kept for safety
         if (rc) return rc;
-        if (E.train && b.count <= (double)BN_SMALL_COUNT)   // small tensors (pooled ASPP branch, 2x2 .. 16x16 maps): exact two-pass statistics
+        if (frozen)   // the conv epilogues still fill their slabs (the training launches as they are); nobody reads them, no buffer is written
+          HIPCHK(launch_bn_finalize_frozen(b.C, gamma, beta, E.buffers + b.rm_off, E.buffers + b.rv_off, b.eps, E.bn_scale(op.bn), E.bn_shift(op.bn),
+                                           E.bn_mean(op.bn), E.bn_rstd(op.bn), E.bn_coef(op.bn), st));
+        else if (E.train && b.count <= (double)BN_SMALL_COUNT)   // small tensors (pooled ASPP branch, 2x2 .. 16x16 maps): exact two-pass statistics
           HIPCHK(launch_bn_finalize_small(P->dtype, E.act(b.y), (int)b.count, b.C, gamma, beta, E.buffers + b.rm_off, E.buffers + b.rv_off, b.momentum,
                                           b.eps, E.bn_scale(op.bn), E.bn_shift(op.bn), E.bn_mean(op.bn), E.bn_rstd(op.bn), st));
         else if (E.train)

@@ -83,6 +83,11 @@ struct Exec {
   hipStream_t st;
   int train;
   hipStream_t wst = nullptr;  // stream of the weight-gradient launches (side stream or st)
+  // seeded data-only backward (octseg_net_backward_seeded): dL/dlogits comes from the caller, no weight / bias / BatchNorm parameter
+  // gradient is launched (grads == nullptr) and the walk ends in front of op `stop_op` (the producer of the tensor whose gradient is wanted)
+  const float* seed = nullptr;
+  bool data_only = false;
+  int stop_op = -1;
   std::vector<char> ginit;   // backward: has the gradient buffer of tensor t been written yet?
   // first contribution stores, later ones accumulate
   int claim(int t) { const int acc = ginit[t] ? 1 : 0; ginit[t] = 1; return acc; }
@@ -145,6 +150,7 @@ int pack_all_weights(Exec& E, bool fold);                                       
 int run_forward(Exec& E, const float* image, float* logits, int normalize, const float* mean, const float* stdv);
 DiceArgs dice_args(const octseg_plan* P, char* ws, const float* logits, const float* target);                    // plan_backward.cpp
 int run_backward(Exec& E, const float* logits, const float* target, float grad_scale, SliceCtx* S = nullptr);
+int cam_target_op(const octseg_plan* P);   // api.cpp: index of the OP_BN_ACT that writes the output of encoder.layer4's last block, or -1
 
 }  // namespace detail
 }  // namespace octseg

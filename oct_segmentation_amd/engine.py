@@ -112,8 +112,9 @@ class _LayerRef:
         return [(p['name'][len(pre):], self._net._torch_view(p)) for p in self._net.param_table if p['name'].startswith(pre)]
 
     def register_forward_hook(self, *_a, **_k):
-        raise NotImplementedError(f'{self.name}: the gfx950 engine exposes no per-layer activations to hooks (Grad-CAM tooling is '
-                                  f'outside the accelerated path); use engine.debug_tensor() for a conv output')
+        raise NotImplementedError(f'{self.name}: the gfx950 engine exposes no per-layer activations to hooks; class activation maps of '
+                                  f'encoder.layer4[-1] come from oct_segmentation_amd.cam (CAMProcessor), a conv output from '
+                                  f'engine.debug_tensor()')
     register_full_backward_hook = register_forward_hook
 
     def __repr__(self):
@@ -204,6 +205,7 @@ class SegNet(nn.Module):
         self.dtype_code = _dtype_code(compute_dtype)
         self.device = torch.device(device)
         self._plans = {}
+        self._cam_plans = {}   # class activation maps: plans of their own in frozen-BatchNorm mode (cam_forward_backward)
         self.use_graph = use_graph
         self.loss = loss
         # train_step_raw as ONE replayed hipGraph per (B, H, W) plan (octseg_net_train_step + octseg_plan_set_train_graph): the ~800
@@ -319,6 +321,7 @@ class SegNet(nn.Module):
             self.device = self.arena.device
             self._grad_arena = self._grad_arena.to(self.device)
             self._plans = {}
+            self._cam_plans = {}
             self.params_changed()
         return self
 
@@ -636,6 +639,52 @@ class SegNet(nn.Module):
         torch.cuda.current_stream(gout.device).wait_stream(gstream)
         plan.graph_pending = False
         return gout.clone()
+
+    # ------------------------------------------------------------------ class activation maps (oct_segmentation_amd.cam)
+    def _cam_plan(self, B, H, W):
+        """A plan of its own per (B, H, W) in frozen-BatchNorm mode: apart from a captured serving graph, from the eval plans' BatchNorm-folded
+        weight images and from the training plans' stale-step generation counter."""
+        key = (B, H, W)
+        if key not in self._cam_plans:
+            plan = _Plan(self.arch, self.encoder_name, self.classes, B, H, W, self.dtype_code)
+            lib = L.lib()
+            rc = lib.octseg_plan_set_frozen_bn(plan.handle, 1)
+            if rc in (-2, -3):
+                raise NotImplementedError(lib.octseg_last_error().decode())
+            L.check(rc)
+            act, gr, dims = C.c_size_t(), C.c_size_t(), (C.c_int * 4)()
+            L.check(lib.octseg_plan_cam_target(plan.handle, C.byref(act), C.byref(gr), dims))
+            plan.cam_target = (act.value, gr.value, tuple(dims))
+            self._cam_plans[key] = plan
+        return self._cam_plans[key]
+
+    def cam_forward_backward(self, x, dlogits, normalize=False, mean=None, std=None):
+        """Forward with every BatchNorm on its running statistics and the activations kept, then the data-only backward of
+        L = sum(logits * dlogits) down to encoder.layer4[-1].  Returns (logits, A, G): A = that block's output, G = dL/dA, views
+        [B, h, w, K] in the compute dtype into the CAM plan's workspace (valid until the next call with this shape).  Parameters, buffers,
+        num_batches_tracked and the gradient arena are left alone."""
+        x = self._check_input(x)
+        B, _, H, W = x.shape
+        if not (torch.is_tensor(dlogits) and dlogits.is_cuda and dlogits.dtype == torch.float32 and tuple(dlogits.shape) == (B, self.classes, H, W)):
+            raise ValueError(f'dlogits must be a float32 CUDA tensor {(B, self.classes, H, W)}')
+        dlogits = dlogits.contiguous()
+        plan = self._cam_plan(B, H, W)
+        ver = (self.arena._version, self._param_epoch)
+        if getattr(plan, 'seen_version', None) != ver:
+            L.check(L.lib().octseg_plan_params_changed(plan.handle))
+            plan.seen_version = ver
+        m = (C.c_float * 3)(*([float(v) for v in mean] if normalize else [0, 0, 0]))
+        s = (C.c_float * 3)(*([float(v) for v in std] if normalize else [1, 1, 1]))
+        logits = torch.empty((B, self.classes, H, W), dtype=torch.float32, device=x.device)
+        ws = plan.ws(x.device)
+        L.check(L.lib().octseg_net_forward(plan.handle, L.ptr(self.arena.data), L.ptr(self.bn_buffers), L.ptr(ws), L.ptr(x), L.ptr(logits),
+                                           int(bool(normalize)), m, s, 1, L.stream_ptr()))
+        L.check(L.lib().octseg_net_backward_seeded(plan.handle, L.ptr(self.arena.data), L.ptr(ws), L.ptr(dlogits), L.stream_ptr()))
+        act, gr, (N, h, w, K) = plan.cam_target
+        tdt = torch.float32 if self.dtype_code == L.F32 else torch.bfloat16
+        nbytes = N * h * w * K * (4 if self.dtype_code == L.F32 else 2)
+        view = lambda off: ws[off:off + nbytes].view(tdt).view(N, h, w, K)   # noqa: E731
+        return logits, view(act), view(gr)
 
     def dice(self, plan, logits, target):
         target = target.contiguous()

@@ -5,7 +5,7 @@
 // counts and the one-launch pack / BN job tables of csrc/plan_geom.cpp and csrc/plan_build.cpp -- ~1400 lines of index arithmetic -- run for every architecture x
 // encoder pair at the smallest legal frame, the benchmark frame and a non-square one, in all three dtypes, with no kernel launched
 // (no GPU needed).  A subset of the plans is then driven through octseg_net_forward / _backward / _backward_sliced / octseg_optim_step and
-// the graph-captured eval forward against tools/hip_host_stubs.cpp, a recording stand-in for the HIP runtime that checks every launch
+// the graph-captured eval forward, and the class-activation-map path (frozen forward, seeded backward, map launches) against tools/hip_host_stubs.cpp, a recording stand-in for the HIP runtime that checks every launch
 // geometry and every memset / copy range.  Exit code 0 = the sanitizers and the stubs saw nothing.
 #include <cstdio>
 #include <cstring>
@@ -80,6 +80,30 @@ int exercise(const octseg_net_desc& d, octseg_plan* p) {
     if (octseg_net_forward(p, params, bufs, wsp, image, logits, 0, nullptr, nullptr, 0, st) != 0) return 20;
   octseg_plan_set_graph(p, 0);
   if (dry_launches() - l0 < 50) { fprintf(stderr, "suspiciously few launches\n"); return 21; }
+  // class activation maps: the frozen-BatchNorm forward, the seeded data-only backward (null gradient arena) and the map launches on the
+  // target tensor, where the pair is built; every other pair must refuse the mode
+  const int frc = octseg_plan_set_frozen_bn(p, 1);
+  if (frc == 0) {
+    size_t ao = 0, go = 0; int dm[4] = {0, 0, 0, 0};
+    if (octseg_plan_cam_target(p, &ao, &go, dm) != 0) return 22;
+    const size_t bytes = (size_t)dm[0] * dm[1] * dm[2] * dm[3] * (d.dtype == OCTSEG_F32 ? 4 : 2);
+    if (dm[0] != d.batch || ao + bytes > ws || go + bytes > ws) { fprintf(stderr, "the CAM target leaves the workspace\n"); return 22; }
+    if (octseg_net_forward(p, params, bufs, wsp, image, logits, 1, mean, stdv, 1, st) != 0) { fprintf(stderr, "frozen forward: %s\n", octseg_last_error()); return 23; }
+    if (octseg_net_backward_seeded(p, params, wsp, target, st) != 0) { fprintf(stderr, "seeded backward: %s\n", octseg_last_error()); return 24; }
+    const int S = d.height;
+    void* scratch = carve(octseg_cam_scratch_bytes(dm[0], dm[1], dm[2], dm[3]));
+    float* maps = (float*)carve((size_t)dm[0] * S * S * 4);
+    uint8_t* bin = (uint8_t*)carve((size_t)dm[0] * S * S); uint8_t* ov = (uint8_t*)carve((size_t)dm[0] * S * S * 3);
+    uint8_t* gt = (uint8_t*)carve((size_t)dm[0] * 75 * 50); int* rows = (int*)carve(75 * 4); int* cols = (int*)carve(50 * 4); int* counts = (int*)carve((size_t)dm[0] * 12);
+    float* frames = (float*)carve((size_t)dm[0] * 3 * S * S * 4); uint8_t* jet = (uint8_t*)carve(768);
+    for (int method = 0; method < 6; ++method)
+      if (octseg_cam_maps(d.dtype, (char*)wsp + ao, (char*)wsp + go, dm[0], dm[1], dm[2], dm[3], method, S, scratch, maps, 0.5f, bin, gt, 75, 50, rows, cols,
+                          counts, frames, jet, 0.5, ov, st) != 0) { fprintf(stderr, "cam_maps: %s\n", octseg_last_error()); return 25; }
+    if (octseg_cam_overlay(maps, frames, jet, dm[0], S, 0.5, ov, scratch, st) != 0) return 25;
+    octseg_plan_set_frozen_bn(p, 0);
+  } else if (frc != OCTSEG_UNSUPPORTED_ARCH && frc != OCTSEG_BAD_DTYPE) {
+    return 26;
+  }
   return 0;
 }
 }  // namespace
