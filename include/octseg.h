@@ -37,6 +37,9 @@
  *                                      maps (src/models/smp/model.py:208-271, called from on_validation_epoch_end, model.py:134-148)
  *   octseg_stack_measure               the measurements of the app's get_analysis: set pixels per slice and class, and the ray walk of
  *                                      calculate_object_thickness per slice, class and degree (src/app/tools/analysis.py:60-130,189,199-200)
+ *   octseg_volume_normalize            cv2.normalize(slice, None, 0, 255, NORM_MINMAX, CV_8U) + cvtColor(BGR2RGB) of every slice of a DICOM's
+ *                                      pixel_array (src/data/convert_dicoms.py:71-81, src/app/tools/analysis.py:167-177)
+ *   octseg_resize_pil_u8               data_processing's Image.open(p).resize(output_size), Pillow's default BICUBIC (src/data/utils.py:187)
  *   octseg_plan_set_frozen_bn / octseg_plan_cam_target / octseg_net_backward_seeded / octseg_cam_maps
  *                                      CAMProcessor.extract_activation_map / overlay_activation_map over pytorch-grad-cam on model.eval()
  *                                      (src/models/cam_processor.py:83-98, src/models/visualize_activation_maps.py:102-199)
@@ -284,6 +287,37 @@ int octseg_epoch_panels(const float* frames, const float* logits, const uint8_t*
  * H * W >= 2^31: OCTSEG_BAD_SHAPE. */
 int octseg_stack_measure(const float* stack, int N, int H, int W, int stack_channels, const int* ray_pix, const int* ray_len, int R, int* counts,
                          int* radii, void* stream);
+
+/* The arithmetic between a DICOM's pixel_array and the frames the pipeline takes (reference src/data/convert_dicoms.py:71-81, repeated in
+ * src/app/tools/analysis.py:167-177): per slice cv2.normalize(img, None, alpha=0, beta=255, norm_type=NORM_MINMAX, dtype=CV_8U), then
+ * cvtColor(BGR2RGB).  src: device [S][H][W][C], uint8 (src_dtype 0) or uint16 (src_dtype 1, 2-byte aligned), C = 1 or 3.
+ * minmax: device uint32 [S][2], scratch AND output: the call sets it to (0xffffffff, 0), then holds the minimum and maximum of every slice over
+ * ALL its channels (minMaxIdx on a multi-channel Mat without an index request).  dst: uint8 [S][H][W][3], must not overlap src.  The
+ * pair is read back on the device, no host synchronisation.  Per slice, in double:
+ *   scale = 255 * (smax - smin > DBL_EPSILON ? 1 / (smax - smin) : 0),  shift = 0 - smin * scale,  a = (float)scale,  b = (float)shift;
+ * per sample dst = saturate_cast<uchar>(rint(x * a + b)), the product and the sum EACH rounded to float32 (OpenCV 4.8.1's baseline convertTo;
+ * its AVX2 build fuses them and can differ by one grey level on a rounding tie -- this form is the one fixed here), rint half to even.
+ * A constant slice comes out 0, a slice spanning 0..255 unchanged.  swap_rb != 0 reverses the three channels; C = 1 is written to three equal
+ * channels.  Parity with cv2 itself is not pinned (cv2 is not installed where this project runs); the tests hold the kernel to a numpy
+ * restatement of the lines above, exactly.
+ * Enqueue only (three launches).  Null pointer: OCTSEG_BAD_ARG; src_dtype not 0 / 1: OCTSEG_BAD_DTYPE; S, H, W <= 0, C not 1 / 3, or a source or
+ * destination frame of 2^31 bytes or more: OCTSEG_BAD_SHAPE.  Nothing is launched then. */
+int octseg_volume_normalize(const void* src, int src_dtype, int S, int H, int W, int C, int swap_rb, unsigned* minmax, uint8_t* dst, void* stream);
+
+/* Image.resize((ow, oh)) of Pillow for 8-bit frames with its default filter, BICUBIC (reference src/data/utils.py:187: data_processing), for a
+ * batch: ImagingResample's two passes (Resample.c), horizontal first, from host tables (oct_segmentation_amd/pullback.py pil_resample_table =
+ * precompute_coeffs + normalize_coeffs_8bpc).  src: uint8 [S][H][W][C], C = 1 (mode L) or 3 (RGB); dst: uint8 [S][oh][ow][C]; tmp: uint8
+ * [S][H][ow][C], read and written only when both axes change (may be null otherwise).  Per axis: bounds device int32 [out][2] = first source
+ * index and tap count of every output index, kk device int32 [out][ksize] = the taps' coefficients at 22 fractional bits.  Per output sample
+ *   ss = (1 << 21) + sum over t < count of src[first + t] * kk[t]  in 32-bit arithmetic,  out = clamp(ss >> 22, 0, 255), arithmetic shift
+ * (bicubic taps overshoot: the clamp is live).  An axis whose output length equals its input length is skipped and its tables may be null, as
+ * Pillow skips it; with both skipped dst is a copy of src.  Bounds outside the source and counts beyond ksize or the source's end are clamped
+ * on the device: a wrong table gives wrong samples, never a stray read.  Integer arithmetic: the result EQUALS Pillow's, no tolerance.
+ * Enqueue only (a launch per resampled axis).  Null src / dst, null tmp when both axes change, null tables of a resampled axis: OCTSEG_BAD_ARG;
+ * S, H, W, oh, ow <= 0, C not 1 / 3, ksize <= 0 for a resampled axis, or a source, intermediate or destination frame of 2^31 bytes or more:
+ * OCTSEG_BAD_SHAPE.  Nothing is launched then. */
+int octseg_resize_pil_u8(const uint8_t* src, int S, int H, int W, int C, uint8_t* tmp, uint8_t* dst, int oh, int ow, const int* xbounds,
+                         const int* xkk, int xksize, const int* ybounds, const int* ykk, int yksize, void* stream);
 
 /* Class activation maps (reference src/models/cam_processor.py:83-98 and src/models/visualize_activation_maps.py:102-199 over the
  * pytorch-grad-cam package; restated in DESIGN.md section 5e, parity with the package itself is not pinned).

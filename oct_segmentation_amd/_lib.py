@@ -88,6 +88,9 @@ SYMBOLS = {
     'octseg_epoch_panels': (C.c_int, [_P, _P, _P] + [C.c_int] * 6 + [_P] * 8),
     # float32 mask stack + host ray table -> int32 set-pixel counts and per-degree radii (csrc/measure.hip)
     'octseg_stack_measure': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P]),
+    # raw volume [S,H,W,C] uint8 | uint16 -> per-slice min / max + uint8 RGB frames; Pillow's 8-bit bicubic resize from tables (csrc/volume.hip)
+    'octseg_volume_normalize': (C.c_int, [_P] + [C.c_int] * 6 + [_P, _P, _P]),
+    'octseg_resize_pil_u8': (C.c_int, [_P] + [C.c_int] * 4 + [_P, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, C.c_int, _P]),
     # class activation maps: frozen-BatchNorm forward, seeded data-only backward, the map kernels (csrc/cam.hip)
     'octseg_plan_set_frozen_bn': (C.c_int, [_P, C.c_int]),
     'octseg_plan_cam_target': (C.c_int, [_P, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),

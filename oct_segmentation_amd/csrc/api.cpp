@@ -293,6 +293,33 @@ int octseg_stack_measure(const float* stack, int N, int H, int W, int stack_chan
   return OCTSEG_OK;
 }
 
+// Raw pullback volumes (data/convert_dicoms.py:71-81, app/tools/analysis.py:167-177; data/utils.py:187): see volume.hip.  Enqueue only.
+int octseg_volume_normalize(const void* src, int src_dtype, int S, int H, int W, int C, int swap_rb, unsigned* minmax, uint8_t* dst, void* stream) {
+  if (!src || !minmax || !dst) return fail(OCTSEG_BAD_ARG, "null argument");
+  if (src_dtype != 0 && src_dtype != 1) return fail(OCTSEG_BAD_DTYPE, "volume_normalize: src_dtype must be 0 (uint8) or 1 (uint16)");
+  if (S <= 0 || H <= 0 || W <= 0) return fail(OCTSEG_BAD_SHAPE, "volume_normalize: empty volume or frame");
+  if (C != 1 && C != 3) return fail(OCTSEG_BAD_SHAPE, "volume_normalize: 1 or 3 channels");
+  if ((long long)H * W * C * (src_dtype ? 2 : 1) >= (1ll << 31) || (long long)H * W * 3 >= (1ll << 31))
+    return fail(OCTSEG_BAD_SHAPE, "volume_normalize: a frame must stay below 2^31 bytes");
+  if (src_dtype == 1 && ((uintptr_t)src & 1)) return fail(OCTSEG_BAD_ARG, "volume_normalize: a uint16 volume must be 2-byte aligned");
+  HIPCHK(launch_volume_normalize(src, src_dtype, S, H, W, C, swap_rb != 0, minmax, dst, (hipStream_t)stream));
+  return OCTSEG_OK;
+}
+
+int octseg_resize_pil_u8(const uint8_t* src, int S, int H, int W, int C, uint8_t* tmp, uint8_t* dst, int oh, int ow, const int* xbounds,
+                         const int* xkk, int xksize, const int* ybounds, const int* ykk, int yksize, void* stream) {
+  const bool horizontal = ow != W, vertical = oh != H;
+  if (!src || !dst || (horizontal && vertical && !tmp)) return fail(OCTSEG_BAD_ARG, "null argument");
+  if (S <= 0 || H <= 0 || W <= 0 || oh <= 0 || ow <= 0) return fail(OCTSEG_BAD_SHAPE, "resize_pil_u8: empty batch or frame");
+  if (C != 1 && C != 3) return fail(OCTSEG_BAD_SHAPE, "resize_pil_u8: 1 or 3 channels");
+  if ((long long)H * W * C >= (1ll << 31) || (long long)H * ow * C >= (1ll << 31) || (long long)oh * ow * C >= (1ll << 31))
+    return fail(OCTSEG_BAD_SHAPE, "resize_pil_u8: a frame must stay below 2^31 bytes");
+  if ((horizontal && (!xbounds || !xkk)) || (vertical && (!ybounds || !ykk))) return fail(OCTSEG_BAD_ARG, "null table of a resampled axis");
+  if ((horizontal && xksize <= 0) || (vertical && yksize <= 0)) return fail(OCTSEG_BAD_SHAPE, "resize_pil_u8: ksize of a resampled axis");
+  HIPCHK(launch_resize_pil_u8(src, S, H, W, C, tmp, dst, oh, ow, xbounds, xkk, xksize, ybounds, ykk, yksize, (hipStream_t)stream));
+  return OCTSEG_OK;
+}
+
 // ---------------------------------------------------------------- class activation maps (cam.hip)
 // Which graphs the frozen-BatchNorm mode and the seeded backward are built for, and why not the others.
 static int cam_supported(const octseg_plan* p) {

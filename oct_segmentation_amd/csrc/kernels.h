@@ -325,6 +325,13 @@ hipError_t launch_epoch_panels(const float* frames, const float* logits, const u
 hipError_t launch_stack_measure(const float* stack, int N, int H, int W, int SC, const int* ray_pix, const int* ray_len, int R, int* counts,
                                 int* radii, hipStream_t st);
 
+// raw pullback volumes (volume.hip): per-slice min / max + cv2.normalize(NORM_MINMAX, CV_8U) + channel order into uint8 [S][H][W][3] (one init,
+// two launches), and Pillow's 8-bit two-pass resample from host tables (a launch per axis that changes length; a copy when none does)
+hipError_t launch_volume_normalize(const void* src, int src_u16, int S, int H, int W, int C, int swap_rb, unsigned* minmax, uint8_t* dst,
+                                   hipStream_t st);
+hipError_t launch_resize_pil_u8(const uint8_t* src, int S, int H, int W, int C, uint8_t* tmp, uint8_t* dst, int oh, int ow, const int* xbounds,
+                                const int* xkk, int xksize, const int* ybounds, const int* ykk, int yksize, hipStream_t st);
+
 // class activation maps (cam.hip).  launch_cam_seed: dL/dlogits NCHW f32 [B][C][HW] -> NHWC T rows padded to CP channels (launch_dice_bwd's layout).
 hipError_t launch_cam_seed(int dtype, const float* seed, void* dlogits, int B, int C, size_t HW, int CP, hipStream_t st);
 // launch_cam_maps: A, G NHWC T [N][h][w][K] -> maps f32 [N][S][S] in [0, 1] and, where the pointers are set, the thresholded map, the confusion

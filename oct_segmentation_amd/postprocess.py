@@ -154,11 +154,15 @@ def epoch_panels(frames_f32, logits, gt_u8, classes, labels=True):
 
 
 def save_results(images, masks, images_name, classes, save_dir, close_iterations=1, device='cuda'):
-    """utils.py:195-235.  ``images``: PIL images at output size.  They are converted to RGB: the reference pastes into whatever mode
+    """utils.py:195-235.  ``images``: PIL images at output size, or the same frames as a uint8 CUDA tensor [n, H, W, 3] (RGB), which skips the
+    upload.  PIL images are converted to RGB: the reference pastes into whatever mode
     ``Image.open`` gave, and for other modes (L, RGBA, P) PIL's paste of an RGB colour behaves differently; RGB is what the demo frames are.
     ``masks``: the list of numpy [H, W, 4] arrays ``segment`` returns, or the device stack [n, H, W, 4] of ``segment_stack`` (then the masks
     never visit the host).  Masks must be 0 / 1 -- what ``segment`` produces and what makes the arithmetic exact; anything else raises
     ``ValueError``.  One upload, one launch, one device-to-host copy of uint8, then ``{name}_mask.png`` and ``{name}_overlay.png`` through PIL."""
+    frames = None
+    if torch.is_tensor(images):       # uint8 RGB frames that are on the device already: no upload (render_results checks them)
+        frames = images
     images, images_name = list(images), list(images_name)
     if torch.is_tensor(masks):
         stack = masks
@@ -179,10 +183,11 @@ def save_results(images, masks, images_name, classes, save_dir, close_iterations
     if torch.is_tensor(masks) and not bool(((stack == 0) | (stack == 1)).all()):
         raise ValueError('masks must hold only 0 and 1')
     h, w = int(stack.shape[1]), int(stack.shape[2])
-    for img in images:
-        if img.size != (w, h):
-            raise ValueError(f'image size {img.size} does not match the masks ({w}, {h})')
-    frames = torch.from_numpy(np.stack([np.asarray(img.convert('RGB')) for img in images])).to(dev)
+    if frames is None:
+        for img in images:
+            if img.size != (w, h):
+                raise ValueError(f'image size {img.size} does not match the masks ({w}, {h})')
+        frames = torch.from_numpy(np.stack([np.asarray(img.convert('RGB')) for img in images])).to(dev)
     overlay, color_mask = render_results(frames, stack, classes, close_iterations)
     out = torch.stack([overlay, color_mask]).cpu().numpy()
     os.makedirs(save_dir, exist_ok=True)

@@ -152,15 +152,22 @@ def segment_stack(images, output_size, classes, models_dir, device='cuda', batch
                   device_preprocess=False):
     """``segment()`` up to and including the mask assembly, with the result left where it was made: the float32 0 / 1 stack
     [n, output_size[0], output_size[1], 4] on the device (channel = CLASS_ID - 1; classes that were not asked for stay 0).  What
-    ``postprocess.save_results`` / ``render_results`` take; ``segment()`` copies it to the host arrays of the reference's interface."""
+    ``postprocess.save_results`` / ``render_results`` take; ``segment()`` copies it to the host arrays of the reference's interface.
+    ``images``: the list of PIL images, or a uint8 CUDA tensor [n, H, W, 3] of RGB frames, which takes the device-preprocess path as it is."""
     from . import _lib as L
+    frames_u8 = None
+    if torch.is_tensor(images):     # frames that are on the device already (pullback.normalize_volume / resize_pil_u8): nothing to upload
+        if not (images.is_cuda and images.dtype == torch.uint8 and images.dim() == 4 and images.shape[3] == 3 and images.shape[0] > 0):
+            raise ValueError('a frame tensor must be a non-empty uint8 CUDA tensor [n, H, W, 3] (RGB)')
+        frames_u8, device, device_preprocess = images.contiguous(), images.device, True
     n = len(images)
     # cv2 sizes are (width, height); the reference allocates masks as [output_size[0], output_size[1], 4] and resizes
     # to tuple(output_size): the assignment into mask[:, :, c] only works for square sizes, and so do the extents below
     oh, ow = int(output_size[0]), int(output_size[1])
     stack = torch.zeros((n, oh, ow, 4), dtype=torch.float32, device=device)
     cache, tables, loaded = {}, {}, {}
-    frames_u8 = _upload_frames_u8(images, device) if device_preprocess else None
+    if frames_u8 is None and device_preprocess:
+        frames_u8 = _upload_frames_u8(images, device)
     for class_name in classes:     # every distinct model once: weights and the preprocessed frames at that model's input size
         model_dir = os.path.join(models_dir, MODELS_META[class_name]['model_dir'])
         if model_dir not in loaded:
@@ -235,6 +242,52 @@ def data_processing(image_paths, output_size):
     return images, masks
 
 
+def _frames_on_device(image_paths, output_size, device):
+    """``data_processing`` with the resize on the GPU: every file whose PIL mode is ``RGB`` or ``L`` goes up at SOURCE size and is resized by
+    ``pullback.resize_pil_u8`` (equal to ``Image.resize`` byte for byte; an ``L`` frame is spread to three channels afterwards, as
+    ``convert('RGB')`` does).  Other modes keep the host ``Image.resize``: Pillow resizes ``P`` with NEAREST and ``RGBA`` premultiplied.
+    Returns the frames at output size, uint8 CUDA [n, output_size[1], output_size[0], 3] in path order."""
+    from .pullback import resize_pil_u8
+    ow, oh = int(output_size[0]), int(output_size[1])          # Image.resize takes (width, height)
+    frames = torch.empty((len(image_paths), oh, ow, 3), dtype=torch.uint8, device=device)
+    groups = {}
+    for i, p in enumerate(image_paths):
+        img = Image.open(p)
+        if img.mode in ('RGB', 'L'):
+            a = np.asarray(img)
+            groups.setdefault(a.shape, []).append((i, a))
+        else:
+            frames[i] = torch.from_numpy(np.array(img.resize((ow, oh)).convert('RGB'))).to(device)
+    for items in groups.values():
+        src = np.stack([a for _, a in items])
+        out = resize_pil_u8(torch.from_numpy(src.reshape(src.shape[:3] + (-1,))).to(device), (oh, ow))
+        frames[torch.tensor([i for i, _ in items], device=device)] = out.expand(-1, -1, -1, 3)
+    return frames
+
+
+def _main_volume(cfg, device, dtypes, log):
+    """``data_dir`` is a ``.npy`` file: a raw volume [S,H,W,3] | [S,H,W], uint8 | uint16 (a DICOM's ``pixel_array``), through
+    ``pullback.analyze_pullback``.  Slice ``k`` (from 1) is written as ``{stem}_{k:03d}_mask.png`` / ``_overlay.png``, the names
+    convert_dicoms gives its frames."""
+    from .pullback import analyze_pullback
+    path = str(cfg['data_dir'])
+    volume = np.load(path)
+    stem = os.path.basename(path).split('.')[0]
+    names = [f'{stem}_{k + 1:03d}' for k in range(volume.shape[0])]
+    log.info(f'Number of slices: {len(names)}')
+    res = analyze_pullback(volume, str(cfg['models_dir']), cfg['classes'], output_size=cfg['output_size'], names=names, render=True,
+                           close_iterations=int(cfg.get('close_iterations', 1)), device=device, batch_size=int(cfg.get('batch_size', 8)),
+                           compute_dtype=dtypes[str(cfg.get('compute_dtype', 'bf16'))], use_graph=bool(cfg.get('use_graph', False)))
+    out = torch.stack([res.overlay, res.color_mask]).cpu().numpy()
+    save_dir = str(cfg['save_dir'])
+    for i, name in enumerate(names):
+        Image.fromarray(out[1, i]).save(f'{save_dir}/{name}_mask.png')
+        Image.fromarray(out[0, i]).save(f'{save_dir}/{name}_overlay.png')
+    if bool(cfg.get('analysis', False)):
+        with open(os.path.join(save_dir, 'analysis.json'), 'w') as f:
+            json.dump(res.data, f)
+
+
 def _image_paths(data_path):
     """data/utils.py:175-178: one file, or the directory's ``*.[pj][np][ge]*`` (png, jpg, jpeg ...)."""
     if os.path.isfile(data_path):
@@ -249,7 +302,10 @@ def main(argv=None):
     (``segment_stack`` -> ``postprocess.save_results``); what comes back is the uint8 overlay and colour mask, 6 bytes per pixel instead of the
     16 of the float32 stack.  Extra keys: ``compute_dtype`` (bf16 | fp16 | fp32), ``batch_size``, ``use_graph``, ``close_iterations``, and
     ``analysis`` (default false): also write ``{save_dir}/analysis.json``, the dict of the app's ``get_analysis`` measured on the same stack
-    (``analysis.analyze_stack``), with the frames as the slices of one pullback in sorted file-name order, as the app sorts its mask files."""
+    (``analysis.analyze_stack``), with the frames as the slices of one pullback in sorted file-name order, as the app sorts its mask files;
+    ``device_resize`` (default true): ``RGB`` and ``L`` files go up at source size and ``data_processing``'s ``Image.resize`` runs on the GPU
+    (``pullback.resize_pil_u8``, byte-identical; false restores the host resize for every file).  A ``data_dir`` that is a ``.npy`` file is a
+    raw volume (a DICOM's ``pixel_array``) and goes through ``pullback.analyze_pullback``: see ``_main_volume``."""
     import logging
     import sys
     import time
@@ -268,7 +324,15 @@ def main(argv=None):
     if not paths:
         raise FileNotFoundError(f'no images under {cfg["data_dir"]}')
     os.makedirs(str(cfg['save_dir']), exist_ok=True)
-    images, _ = data_processing(paths, cfg['output_size'])
+    if str(cfg['data_dir']).endswith('.npy'):
+        _main_volume(cfg, device, dtypes, log)
+        log.info(f'Overall computation time: {time.time() - start:.1f} s')
+        log.info('Complete')
+        return 0
+    if bool(cfg.get('device_resize', True)):
+        images = _frames_on_device(paths, cfg['output_size'], device)
+    else:
+        images, _ = data_processing(paths, cfg['output_size'])
     names = [os.path.basename(p).split('.')[0] for p in paths]
     log.info(f'Number of images: {len(names)}')
     start_inference = time.time()
