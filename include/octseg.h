@@ -37,6 +37,9 @@
  *                                      maps (src/models/smp/model.py:208-271, called from on_validation_epoch_end, model.py:134-148)
  *   octseg_stack_measure               the measurements of the app's get_analysis: set pixels per slice and class, and the ray walk of
  *                                      calculate_object_thickness per slice, class and degree (src/app/tools/analysis.py:60-130,189,199-200)
+ *   octseg_stack_components / octseg_stack_cleanup / octseg_components_scratch_bytes
+ *                                      MaskProcessor.smooth_mask / .remove_artifacts, which process_pair runs over every annotated object
+ *                                      (src/data/mask_processor.py:5-37, src/data/convert_int_to_cv.py:191-199)
  *   octseg_volume_normalize            cv2.normalize(slice, None, 0, 255, NORM_MINMAX, CV_8U) + cvtColor(BGR2RGB) of every slice of a DICOM's
  *                                      pixel_array (src/data/convert_dicoms.py:71-81, src/app/tools/analysis.py:167-177)
  *   octseg_resize_pil_u8               data_processing's Image.open(p).resize(output_size), Pillow's default BICUBIC (src/data/utils.py:187)
@@ -287,6 +290,33 @@ int octseg_epoch_panels(const float* frames, const float* logits, const uint8_t*
  * H * W >= 2^31: OCTSEG_BAD_SHAPE. */
 int octseg_stack_measure(const float* stack, int N, int H, int W, int stack_channels, const int* ray_pix, const int* ray_len, int R, int* counts,
                          int* radii, void* stream);
+
+/* Mask clean-up (reference src/data/mask_processor.py:5-37: MaskProcessor.smooth_mask and .remove_artifacts, run by process_pair,
+ * src/data/convert_int_to_cv.py:191-199), on connected components by pixel count (DESIGN.md section 5g states how that differs from
+ * cv2.contourArea over RETR_TREE contours).  stack: device f32 [N][H][W][channels], any value != 0 is set; a plane is one (slice, channel) pair.
+ * scratch: device, scratch_bytes >= octseg_components_scratch_bytes(N * channels, H, W) (0 for extents the calls refuse), 8-byte aligned.
+ *
+ * octseg_stack_components: the 8-connected foreground components of every plane.  Optional outputs (null = skipped, at least one):
+ *   labels int32 [N][channels][H][W]: 1 + y * W + x of the component's first pixel in raster order, background 0;
+ *   ncomp  int32 [N][channels]: the number of components;
+ *   top    int32 [N][channels][8][6]: the 8 largest, area descending then first pixel ascending; columns area, first_pixel (y * W + x), x0, y0,
+ *          x1, y1 (inclusive bounding box); rows beyond ncomp are zero.
+ *
+ * octseg_stack_cleanup: out f32 [N][H][W][channels] (0.0 / 1.0, must not alias stack) =
+ *   smooth_k >= 2: smooth_mask's chain erode, dilate, dilate, erode, dilate with cv2.getStructuringElement(MORPH_ELLIPSE, (k, k)), anchor k / 2,
+ *     the element not reflected, outside the frame not taking part (smooth_k 0 or 1: skipped; the reference's k = max(int(0.005 * min(H, W)), 1));
+ *   keep > 0: t = the keep-th largest area of the plane (0 with fewer components); components with area >= t stay, ties at t all stay (the
+ *     reference's `area in sorted_areas`); min_area additionally drops components with area < min_area; keep = 0: no rank filter;
+ *   fill_holes != 0: every background pixel of the kept mask that is not 4-connected to the frame border through background is set
+ *     (scipy.ndimage.binary_fill_holes; what drawContours(FILLED) of outer contours does).
+ * ncomp / top (optional) describe the kept components after the filter and before the fill, in the layout above.
+ * Enqueue only, nothing is allocated.  Null stack / scratch / out, no output requested, scratch too small or misaligned, negative keep / min_area, out ==
+ * stack: OCTSEG_BAD_ARG; N, H, W <= 0, channels outside 1..16, H * W >= 2^31 - 1, smooth_k outside 0..7: OCTSEG_BAD_SHAPE.  Nothing is launched then. */
+size_t octseg_components_scratch_bytes(int planes, int H, int W);
+int octseg_stack_components(const float* stack, int N, int H, int W, int channels, void* scratch, size_t scratch_bytes, int* labels, int* ncomp,
+                            int* top, void* stream);
+int octseg_stack_cleanup(const float* stack, int N, int H, int W, int channels, int smooth_k, int keep, int min_area, int fill_holes, void* scratch,
+                         size_t scratch_bytes, float* out, int* ncomp, int* top, void* stream);
 
 /* The arithmetic between a DICOM's pixel_array and the frames the pipeline takes (reference src/data/convert_dicoms.py:71-81, repeated in
  * src/app/tools/analysis.py:167-177): per slice cv2.normalize(img, None, alpha=0, beta=255, norm_type=NORM_MINMAX, dtype=CV_8U), then

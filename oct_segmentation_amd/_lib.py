@@ -88,6 +88,11 @@ SYMBOLS = {
     'octseg_epoch_panels': (C.c_int, [_P, _P, _P] + [C.c_int] * 6 + [_P] * 8),
     # float32 mask stack + host ray table -> int32 set-pixel counts and per-degree radii (csrc/measure.hip)
     'octseg_stack_measure': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P]),
+    # float32 mask stack -> connected components (labels, count, the 8 largest) and the cleaned stack: smooth, keep-largest, hole fill
+    # (csrc/components.hip)
+    'octseg_components_scratch_bytes': (C.c_size_t, [C.c_int] * 3),
+    'octseg_stack_components': (C.c_int, [_P] + [C.c_int] * 4 + [_P, C.c_size_t, _P, _P, _P, _P]),
+    'octseg_stack_cleanup': (C.c_int, [_P] + [C.c_int] * 8 + [_P, C.c_size_t, _P, _P, _P, _P]),
     # raw volume [S,H,W,C] uint8 | uint16 -> per-slice min / max + uint8 RGB frames; Pillow's 8-bit bicubic resize from tables (csrc/volume.hip)
     'octseg_volume_normalize': (C.c_int, [_P] + [C.c_int] * 6 + [_P, _P, _P]),
     'octseg_resize_pil_u8': (C.c_int, [_P] + [C.c_int] * 4 + [_P, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, C.c_int, _P]),

@@ -156,7 +156,7 @@ def build_analysis(counts, radii, h, w, image_names, ratio=None, masks=None):
     return data
 
 
-def analyze_stack(stack, image_names=None, ratio=None, thickness='radial', with_masks=False):
+def analyze_stack(stack, image_names=None, ratio=None, thickness='radial', with_masks=False, clean=None):
     """The app's ``get_analysis`` dict for a mask stack on the device.  NOTE: ``thickness_mean`` / ``thickness_min`` carry the median / min of
     upstream's RADIAL thickness function, ``calculate_object_thickness`` -- not of ``calculate_thickness_contour``, the call ``get_analysis``
     actually makes (analysis.py:202-207), whose result depends on ``cv2.findContours``' border-following order and vertex compression and has
@@ -165,7 +165,9 @@ def analyze_stack(stack, image_names=None, ratio=None, thickness='radial', with_
     ``stack`` float32 CUDA [N, H, W, channels]; ``image_names`` one per slice (default ``'0', '1', ...``), the slices in pullback order.
     Runs ``measure_stack``, makes ONE device-to-host copy of counts and radii (about 6 KB per slice) and calls ``build_analysis``.
     ``with_masks=True`` also fills upstream's ``masks`` lists (base64 PNG of the 0 / 255 uint8 mask, analysis.py:208-211), which copies the
-    present masks to the host; the default leaves the lists empty and the masks on the device."""
+    present masks to the host; the default leaves the lists empty and the masks on the device.
+    ``clean``: None (default, the stack is measured as it is), True or a dict of ``cleanup.clean_stack`` keywords: the stack goes through
+    ``clean_stack`` first (smoothing, keep-largest, hole fill) and the cleaned stack is what is measured and what ``with_masks`` encodes."""
     if thickness == 'contour':
         raise NotImplementedError("thickness='contour' (calculate_thickness_contour) needs cv2.findContours / contourArea / moments: its "
                                   'result depends on OpenCV\'s border-following order, tie-breaking among equal areas and '
@@ -173,6 +175,10 @@ def analyze_stack(stack, image_names=None, ratio=None, thickness='radial', with_
                                   "to; use thickness='radial' (calculate_object_thickness)")
     if thickness != 'radial':
         raise ValueError(f"thickness must be 'radial' or 'contour', got {thickness!r}")
+    from .cleanup import clean_kwargs, clean_stack
+    kw = clean_kwargs(clean)
+    if kw is not None:
+        stack = clean_stack(stack, **kw)
     counts, radii = measure_stack(stack)
     n, h, w, sc = (int(v) for v in stack.shape)
     if image_names is None:

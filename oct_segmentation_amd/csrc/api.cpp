@@ -293,6 +293,43 @@ int octseg_stack_measure(const float* stack, int N, int H, int W, int stack_chan
   return OCTSEG_OK;
 }
 
+// Mask clean-up (data/mask_processor.py:5-37, run by process_pair, data/convert_int_to_cv.py:191-199): see components.hip.  Enqueue only.
+static int components_args(const char* who, const void* stack, int N, int H, int W, int channels, const void* scratch, size_t scratch_bytes) {
+  if (!stack || !scratch) return fail(OCTSEG_BAD_ARG, "null argument");
+  if ((uintptr_t)scratch & 7) return fail(OCTSEG_BAD_ARG, std::string(who) + ": scratch must be 8-byte aligned");
+  if (N <= 0 || H <= 0 || W <= 0 || channels <= 0 || channels > 16)
+    return fail(OCTSEG_BAD_SHAPE, std::string(who) + ": empty batch or frame, or not 1..16 channels");
+  if ((long long)H * W >= (1ll << 31) - 1) return fail(OCTSEG_BAD_SHAPE, std::string(who) + ": H * W must be below 2^31 - 1");
+  if ((long long)N * channels >= (1ll << 31)) return fail(OCTSEG_BAD_SHAPE, std::string(who) + ": N * channels must be below 2^31");
+  if (scratch_bytes < components_scratch_bytes((size_t)N * channels, H, W))
+    return fail(OCTSEG_BAD_ARG, std::string(who) + ": scratch is smaller than octseg_components_scratch_bytes(N * channels, H, W)");
+  return OCTSEG_OK;
+}
+
+size_t octseg_components_scratch_bytes(int planes, int H, int W) {
+  if (planes <= 0 || H <= 0 || W <= 0 || (long long)H * W >= (1ll << 31) - 1) return 0;
+  return components_scratch_bytes((size_t)planes, H, W);
+}
+
+int octseg_stack_components(const float* stack, int N, int H, int W, int channels, void* scratch, size_t scratch_bytes, int* labels, int* ncomp,
+                            int* top, void* stream) {
+  if (const int rc = components_args("stack_components", stack, N, H, W, channels, scratch, scratch_bytes)) return rc;
+  if (!labels && !ncomp && !top) return fail(OCTSEG_BAD_ARG, "stack_components: no output requested");
+  HIPCHK(launch_stack_components(stack, N, H, W, channels, scratch, labels, ncomp, top, (hipStream_t)stream));
+  return OCTSEG_OK;
+}
+
+int octseg_stack_cleanup(const float* stack, int N, int H, int W, int channels, int smooth_k, int keep, int min_area, int fill_holes, void* scratch,
+                         size_t scratch_bytes, float* out, int* ncomp, int* top, void* stream) {
+  if (!out) return fail(OCTSEG_BAD_ARG, "null argument");
+  if (const int rc = components_args("stack_cleanup", stack, N, H, W, channels, scratch, scratch_bytes)) return rc;
+  if (smooth_k < 0 || smooth_k > 7) return fail(OCTSEG_BAD_SHAPE, "stack_cleanup: smooth_k must be 0 (off) or 1..7 (frames whose short side is below 1600)");
+  if (keep < 0 || min_area < 0) return fail(OCTSEG_BAD_ARG, "stack_cleanup: keep and min_area must not be negative");
+  if (out == stack) return fail(OCTSEG_BAD_ARG, "stack_cleanup: the output must not alias the input");
+  HIPCHK(launch_stack_cleanup(stack, N, H, W, channels, smooth_k, keep, min_area, fill_holes ? 1 : 0, scratch, out, ncomp, top, (hipStream_t)stream));
+  return OCTSEG_OK;
+}
+
 // Raw pullback volumes (data/convert_dicoms.py:71-81, app/tools/analysis.py:167-177; data/utils.py:187): see volume.hip.  Enqueue only.
 int octseg_volume_normalize(const void* src, int src_dtype, int S, int H, int W, int C, int swap_rb, unsigned* minmax, uint8_t* dst, void* stream) {
   if (!src || !minmax || !dst) return fail(OCTSEG_BAD_ARG, "null argument");

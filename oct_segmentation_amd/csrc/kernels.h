@@ -325,6 +325,14 @@ hipError_t launch_epoch_panels(const float* frames, const float* logits, const u
 hipError_t launch_stack_measure(const float* stack, int N, int H, int W, int SC, const int* ray_pix, const int* ray_len, int R, int* counts,
                                 int* radii, hipStream_t st);
 
+// mask clean-up (components.hip): connected components of every (slice, channel) plane by union-find on bit planes, the 8 largest with their
+// bounding boxes, keep-largest / min-area filter, hole fill (the same labelling on the complement, 4-connected) and the reference's
+// smooth_mask chain.  scratch: components_scratch_bytes(N * C, H, W) device bytes; labels / ncomp / top are optional (null = skipped)
+size_t components_scratch_bytes(size_t planes, int H, int W);
+hipError_t launch_stack_components(const float* stack, int N, int H, int W, int C, void* scratch, int* labels, int* ncomp, int* top, hipStream_t st);
+hipError_t launch_stack_cleanup(const float* stack, int N, int H, int W, int C, int smooth_k, int keep, int min_area, int fill_holes, void* scratch,
+                                float* out, int* ncomp, int* top, hipStream_t st);
+
 // raw pullback volumes (volume.hip): per-slice min / max + cv2.normalize(NORM_MINMAX, CV_8U) + channel order into uint8 [S][H][W][3] (one init,
 // two launches), and Pillow's 8-bit two-pass resample from host tables (a launch per axis that changes length; a copy when none does)
 hipError_t launch_volume_normalize(const void* src, int src_u16, int S, int H, int W, int C, int swap_rb, unsigned* minmax, uint8_t* dst,

@@ -277,7 +277,8 @@ def _main_volume(cfg, device, dtypes, log):
     log.info(f'Number of slices: {len(names)}')
     res = analyze_pullback(volume, str(cfg['models_dir']), cfg['classes'], output_size=cfg['output_size'], names=names, render=True,
                            close_iterations=int(cfg.get('close_iterations', 1)), device=device, batch_size=int(cfg.get('batch_size', 8)),
-                           compute_dtype=dtypes[str(cfg.get('compute_dtype', 'bf16'))], use_graph=bool(cfg.get('use_graph', False)))
+                           compute_dtype=dtypes[str(cfg.get('compute_dtype', 'bf16'))], use_graph=bool(cfg.get('use_graph', False)),
+                           clean=bool(cfg.get('clean', False)))
     out = torch.stack([res.overlay, res.color_mask]).cpu().numpy()
     save_dir = str(cfg['save_dir'])
     for i, name in enumerate(names):
@@ -303,6 +304,8 @@ def main(argv=None):
     16 of the float32 stack.  Extra keys: ``compute_dtype`` (bf16 | fp16 | fp32), ``batch_size``, ``use_graph``, ``close_iterations``, and
     ``analysis`` (default false): also write ``{save_dir}/analysis.json``, the dict of the app's ``get_analysis`` measured on the same stack
     (``analysis.analyze_stack``), with the frames as the slices of one pullback in sorted file-name order, as the app sorts its mask files;
+    ``clean`` (default false): the mask stack goes through ``cleanup.clean_stack`` (the reference's ``MaskProcessor``: smoothing, the three
+    largest components, hole fill) before it is rendered and measured;
     ``device_resize`` (default true): ``RGB`` and ``L`` files go up at source size and ``data_processing``'s ``Image.resize`` runs on the GPU
     (``pullback.resize_pil_u8``, byte-identical; false restores the host resize for every file).  A ``data_dir`` that is a ``.npy`` file is a
     raw volume (a DICOM's ``pixel_array``) and goes through ``pullback.analyze_pullback``: see ``_main_volume``."""
@@ -339,6 +342,9 @@ def main(argv=None):
     stack = segment_stack(images, cfg['output_size'], cfg['classes'], str(cfg['models_dir']), device=device,
                           batch_size=int(cfg.get('batch_size', 8)), compute_dtype=dtypes[str(cfg.get('compute_dtype', 'bf16'))],
                           use_graph=bool(cfg.get('use_graph', False)), device_preprocess=True)
+    if bool(cfg.get('clean', False)):
+        from .cleanup import clean_stack
+        stack = clean_stack(stack)
     torch.cuda.synchronize()
     log.info(f'Prediction time: {time.time() - start_inference:.1f} s')
     save_results(images, stack, names, cfg['classes'], str(cfg['save_dir']), close_iterations=int(cfg.get('close_iterations', 1)))

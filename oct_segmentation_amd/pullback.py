@@ -158,7 +158,7 @@ def normalize_volume(volume, swap_rb=True, device='cuda', return_minmax=False):
 
 
 def analyze_pullback(volume, models_dir, classes, output_size=(1000, 1000), names=None, render=False, swap_rb=True, close_iterations=1,
-                     **segment_kwargs):
+                     clean=None, **segment_kwargs):
     """From a raw volume to the app's dict in one call: ``normalize_volume`` -> ``resize_pil_u8`` -> ``predict.segment_stack`` ->
     ``analysis.analyze_stack``; with ``render=True`` also ``postprocess.render_results``.  The frames go up once, at source size, and nothing
     comes back but the results.
@@ -167,7 +167,8 @@ def analyze_pullback(volume, models_dir, classes, output_size=(1000, 1000), name
     resized as ``Image.resize(tuple(output_size))`` does, the mask stack is [S, output_size[0], output_size[1], 4] (square sizes, as
     upstream).  ``ratio = int(volume.shape[1] * 150 // 1000)``: the SOURCE height, upstream's ``dcm.shape[1]``, not the output size.
     ``names`` default to ``'001', '002', ...`` (the ``slice+1:03d`` of convert_dicoms).  ``segment_kwargs`` go to ``segment_stack``
-    (``batch_size``, ``compute_dtype``, ``use_graph``, ``device``).
+    (``batch_size``, ``compute_dtype``, ``use_graph``, ``device``).  ``clean``: None (default), True or a dict of ``cleanup.clean_stack``
+    keywords: the mask stack is cleaned once (smoothing, keep-largest, hole fill) and the cleaned stack is measured, rendered and returned.
 
     Returns ``Pullback(data, stack, frames, overlay, color_mask)``: the dict, the float32 mask stack and the uint8 RGB frames at output size
     on the device; overlay and colour mask (uint8 CUDA [S,oh,ow,3]) with ``render=True``, else None."""
@@ -180,6 +181,10 @@ def analyze_pullback(volume, models_dir, classes, output_size=(1000, 1000), name
     if names is None:
         names = [f'{i + 1:03d}' for i in range(S)]
     stack = segment_stack(frames, output_size, classes, models_dir, **segment_kwargs)
+    from .cleanup import clean_kwargs, clean_stack
+    kw = clean_kwargs(clean)
+    if kw is not None:
+        stack = clean_stack(stack, **kw)
     data = analyze_stack(stack, names, ratio=int(H * 150 // 1000))
     overlay = color_mask = None
     if render:
