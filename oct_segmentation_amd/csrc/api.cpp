@@ -564,7 +564,7 @@ int octseg_debug_set_serial(int on) { g_serial = on != 0; g_prof_hbm = g_serial;
 size_t octseg_conv2d_scratch_bytes(int dtype, int N, int H, int W, int Cin, int Cout, int R, int S) {
   // upper bound over stride / transposed variants: both images use rows padded to <= 128 and K to <= 64 elements
   (void)N; (void)H; (void)W;
-  const size_t esz = dtype == OCTSEG_F32 ? 4 : 2;
+  const size_t esz = dtype_size(dtype);
   const size_t rows_f = ((size_t)Cout + 127) / 128 * 128, k_f = ((size_t)Cin + 63) / 64 * 64;
   const size_t rows_d = ((size_t)Cin + 127) / 128 * 128, k_d = ((size_t)Cout + 63) / 64 * 64;
   return align_up((size_t)R * S * rows_f * k_f * esz) + align_up((size_t)R * S * rows_d * k_d * esz);
@@ -592,10 +592,10 @@ int octseg_conv2d_forward(int dtype, const void* x, const float* w, const float*
 
 int octseg_conv2d_backward_data(int dtype, const void* dy, const float* w, void* dx, int N, int H, int W, int Cin,
                                 int Cout, int R, int S, int stride, int pad, int transposed, void* scratch, void* stream) {
-  const int v = dtype == OCTSEG_F32 ? 4 : 8;
+  const int v = ev_vec(dtype);
   if (!geom_ok(dtype, Cin, Cout, R, S, stride, transposed) || Cout % v != 0) return fail(OCTSEG_BAD_SHAPE, "unsupported conv geometry");
   hipStream_t st = (hipStream_t)stream;
-  const size_t esz = dtype == OCTSEG_F32 ? 4 : 2;
+  const size_t esz = dtype_size(dtype);
   const Geom g = op_geom(N, H, W, Cin, Cout, R, S, stride, pad, transposed);
   HIPCHK(hipMemsetAsync(dx, 0, (size_t)N * H * W * Cin * esz, st));
   std::vector<ConvArgs> ld;
@@ -618,7 +618,7 @@ int octseg_conv2d_backward_data(int dtype, const void* dy, const float* w, void*
 
 int octseg_conv2d_backward_weight(int dtype, const void* x, const void* dy, float* dw, int N, int H, int W, int Cin,
                                   int Cout, int R, int S, int stride, int pad, int transposed, void* stream) {
-  const int v = dtype == OCTSEG_F32 ? 4 : 8;
+  const int v = ev_vec(dtype);
   if (!geom_ok(dtype, Cin, Cout, R, S, stride, transposed) || Cout % v != 0) return fail(OCTSEG_BAD_SHAPE, "unsupported conv geometry");
   hipStream_t st = (hipStream_t)stream;
   const Geom g = op_geom(N, H, W, Cin, Cout, R, S, stride, pad, transposed);

@@ -43,8 +43,7 @@ hipError_t launch_cam_seed(int dtype, const float* seed, void* dlogits, int B, i
   OCTSEG_NO_F16(dtype);
   if (C > CP || CP > 16 || CP % 8 != 0) return hipErrorInvalidValue;
   const int gr = grid_for((size_t)B * HW, 256);
-  if (dtype == DT_F32) hipLaunchKernelGGL(cam_seed_kernel<float>, dim3(gr), dim3(256), 0, st, seed, dlogits, B, C, HW, CP);
-  else hipLaunchKernelGGL(cam_seed_kernel<bf16_t>, dim3(gr), dim3(256), 0, st, seed, dlogits, B, C, HW, CP);
+  OCTSEG_LAUNCH_TRAIN(cam_seed_kernel, dim3(gr), dim3(256), seed, dlogits, B, C, HW, CP);
   return hipGetLastError();
 }
 
@@ -284,7 +283,7 @@ size_t cam_scratch_bytes(int N, int h, int w, int K) {
 
 hipError_t launch_cam_maps(int dtype, const CamArgs& c, hipStream_t st) {
   OCTSEG_NO_F16(dtype);
-  const int VEC = dtype == DT_F32 ? 4 : 8;
+  const int VEC = ev_vec(dtype);
   const int hw = c.h * c.w, vpc = c.K / VEC;
   if (c.K % VEC != 0 || c.method < 0 || c.method > 5) return hipErrorInvalidValue;
   float* wts = (float*)c.scratch;
@@ -292,13 +291,11 @@ hipError_t launch_cam_maps(int dtype, const CamArgs& c, hipStream_t st) {
   unsigned* acc = (unsigned*)(raw + (size_t)c.N * hw);
   if (cam_weighted(c.method)) {
     const int g = (c.N * vpc + 255) / 256;
-    if (dtype == DT_F32) hipLaunchKernelGGL(cam_weights_kernel<float>, dim3(g), dim3(256), 0, st, c.A, c.G, wts, c.N, hw, c.K, c.method);
-    else hipLaunchKernelGGL(cam_weights_kernel<bf16_t>, dim3(g), dim3(256), 0, st, c.A, c.G, wts, c.N, hw, c.K, c.method);
+    OCTSEG_LAUNCH_TRAIN(cam_weights_kernel, dim3(g), dim3(256), c.A, c.G, wts, c.N, hw, c.K, c.method);
   }
   {
     const int g = (c.N * hw + 3) / 4;
-    if (dtype == DT_F32) hipLaunchKernelGGL(cam_raw_kernel<float>, dim3(g), dim3(256), 0, st, c.A, c.G, wts, raw, c.N, hw, c.K, c.method);
-    else hipLaunchKernelGGL(cam_raw_kernel<bf16_t>, dim3(g), dim3(256), 0, st, c.A, c.G, wts, raw, c.N, hw, c.K, c.method);
+    OCTSEG_LAUNCH_TRAIN(cam_raw_kernel, dim3(g), dim3(256), c.A, c.G, wts, raw, c.N, hw, c.K, c.method);
   }
   hipLaunchKernelGGL(cam_norm_kernel, dim3(c.N), dim3(256), 0, st, raw, acc, hw);
   const int SS = c.S * c.S;

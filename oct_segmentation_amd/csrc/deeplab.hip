@@ -19,13 +19,6 @@
 
 namespace octseg {
 
-#define DL_DISPATCH(KERNEL, grid, ...)                                                          \
-  do {                                                                                          \
-    if (dtype == DT_F32) hipLaunchKernelGGL(KERNEL<float>, grid, dim3(256), 0, st, __VA_ARGS__);      \
-    else if (dtype == DT_F16) hipLaunchKernelGGL(KERNEL<f16_t>, grid, dim3(256), 0, st, __VA_ARGS__); \
-    else hipLaunchKernelGGL(KERNEL<bf16_t>, grid, dim3(256), 0, st, __VA_ARGS__);                     \
-  } while (0)
-
 template <typename T>
 static __device__ __forceinline__ void put(void* dst, size_t idx, float* x, int accum) {
   constexpr int VEC = EV<T>::VEC;
@@ -58,10 +51,10 @@ __global__ __launch_bounds__(256) void parity_permute_kernel(const void* src, vo
   }
 }
 hipError_t launch_parity_permute(int dtype, const void* src, void* dst, int N, int H, int W, int C, int to_coarse, int accum, hipStream_t st) {
-  const int vec = dtype == DT_F32 ? 4 : 8;
+  const int vec = ev_vec(dtype);
   if (C % vec != 0 || (H & 1) || (W & 1)) return hipErrorInvalidValue;
   const size_t nvec = (size_t)N * H * W * (C / vec);
-  DL_DISPATCH(parity_permute_kernel, dim3(grid_for(nvec, 256)), src, dst, N, H, W, C / vec, to_coarse, accum);
+  OCTSEG_LAUNCH(parity_permute_kernel, dim3(grid_for(nvec, 256)), dim3(256), src, dst, N, H, W, C / vec, to_coarse, accum);
   return hipGetLastError();
 }
 
@@ -102,7 +95,7 @@ __global__ __launch_bounds__(256) void dw_conv_kernel(const DwArgs a) {
   }
 }
 static bool dw_ok(int dtype, const DwArgs& a) {
-  const int vec = dtype == DT_F32 ? 4 : 8;
+  const int vec = ev_vec(dtype);
   return a.C % vec == 0 && a.inC % vec == 0 && a.outC % vec == 0 && a.ic0 % vec == 0 && a.oc0 % vec == 0 && a.wc0 % 4 == 0 && a.wC % 4 == 0 &&
          a.dil >= 1 && a.ic0 + a.C <= a.inC && a.oc0 + a.C <= a.outC && a.wc0 + a.C <= a.wC;
 }
@@ -110,8 +103,8 @@ hipError_t launch_dw_conv(int dtype, const void* in, int inC, int ic0, void* out
                           int W, int C, int dil, int flip, int accum, hipStream_t st) {
   DwArgs a{in, out, w, inC, ic0, outC, oc0, wC, wc0, N, H, W, C, dil, flip, accum};
   if (!dw_ok(dtype, a)) return hipErrorInvalidValue;
-  const size_t nvec = (size_t)N * H * W * (C / (dtype == DT_F32 ? 4 : 8));
-  DL_DISPATCH(dw_conv_kernel, dim3(grid_for(nvec, 256)), a);
+  const size_t nvec = (size_t)N * H * W * (C / ev_vec(dtype));
+  OCTSEG_LAUNCH(dw_conv_kernel, dim3(grid_for(nvec, 256)), dim3(256), a);
   return hipGetLastError();
 }
 
@@ -169,7 +162,7 @@ hipError_t launch_dw_wgrad(int dtype, const void* in, int inC, int ic0, const vo
   OCTSEG_NO_F16(dtype);
   DwArgs a{in, const_cast<void*>(gout), nullptr, inC, ic0, goC, oc0, wC, wc0, N, H, W, C, dil, 0, 0};
   if (!dw_ok(dtype, a)) return hipErrorInvalidValue;
-  const int vpc = C / (dtype == DT_F32 ? 4 : 8);
+  const int vpc = C / ev_vec(dtype);
   const int nv = vpc < DW_CH ? vpc : DW_CH, rows = 256 / nv;
   const size_t npix = (size_t)N * H * W;
   const int nch = (vpc + DW_CH - 1) / DW_CH;
@@ -178,8 +171,7 @@ hipError_t launch_dw_wgrad(int dtype, const void* in, int inC, int ic0, const vo
   if (gx > want) gx = want;
   if (gx < 1 || deterministic_mode()) gx = 1;
   const dim3 grid((unsigned)gx, (unsigned)nch);
-  if (dtype == DT_F32) hipLaunchKernelGGL(dw_wgrad_kernel<float>, grid, dim3(256), 0, st, a, dw);
-  else hipLaunchKernelGGL(dw_wgrad_kernel<bf16_t>, grid, dim3(256), 0, st, a, dw);
+  OCTSEG_LAUNCH_TRAIN(dw_wgrad_kernel, grid, dim3(256), a, dw);
   return hipGetLastError();
 }
 
@@ -217,10 +209,10 @@ __global__ __launch_bounds__(256) void image_sum_kernel(const void* in, void* ou
   }
 }
 hipError_t launch_image_sum(int dtype, const void* in, void* out, int N, int HW, int C, float div, hipStream_t st) {
-  const int vec = dtype == DT_F32 ? 4 : 8;
+  const int vec = ev_vec(dtype);
   if (C % vec != 0) return hipErrorInvalidValue;
   const int vpc = C / vec;
-  DL_DISPATCH(image_sum_kernel, dim3((vpc + DW_CH - 1) / DW_CH, N), in, out, HW, vpc, div);
+  OCTSEG_LAUNCH(image_sum_kernel, dim3((vpc + DW_CH - 1) / DW_CH, N), dim3(256), in, out, HW, vpc, div);
   return hipGetLastError();
 }
 // out[n][p][c] (+)= scale * in[n][c]   (F.interpolate of a 1x1 map to any size, either align_corners: a broadcast; gradient of the mean)
@@ -238,10 +230,10 @@ __global__ __launch_bounds__(256) void image_bcast_kernel(const void* in, void* 
   }
 }
 hipError_t launch_image_bcast(int dtype, const void* in, void* out, int N, int HW, int C, float scale, int accum, hipStream_t st) {
-  const int vec = dtype == DT_F32 ? 4 : 8;
+  const int vec = ev_vec(dtype);
   if (C % vec != 0) return hipErrorInvalidValue;
   const size_t nvec = (size_t)N * HW * (C / vec);
-  DL_DISPATCH(image_bcast_kernel, dim3(grid_for(nvec, 256)), in, out, (size_t)HW, C / vec, scale, accum, nvec);
+  OCTSEG_LAUNCH(image_bcast_kernel, dim3(grid_for(nvec, 256)), dim3(256), in, out, (size_t)HW, C / vec, scale, accum, nvec);
   return hipGetLastError();
 }
 
@@ -261,48 +253,18 @@ __global__ __launch_bounds__(256) void drop_elem_kernel(const void* in, const fl
   }
 }
 hipError_t launch_drop_elem(int dtype, const void* in, const float* keep, float mscale, void* out, size_t numel, hipStream_t st) {
-  const int vec = dtype == DT_F32 ? 4 : 8;
+  const int vec = ev_vec(dtype);
   if (numel % vec != 0) return hipErrorInvalidValue;
   const size_t nvec = numel / vec;
-  DL_DISPATCH(drop_elem_kernel, dim3(grid_for(nvec, 256)), in, keep, mscale, out, nvec);
+  OCTSEG_LAUNCH(drop_elem_kernel, dim3(grid_for(nvec, 256)), dim3(256), in, keep, mscale, out, nvec);
   return hipGetLastError();
 }
 
 // ------------------------------------------------------------------ bilinear resample by `up`, align_corners=True (nn.UpsamplingBilinear2d), NHWC -> NHWC
-// torch's source index: scale = (in - 1) / (out - 1) in float, x = scale * o, i0 = (int)x, lambda1 = x - i0 (as fpn.hip; the adjoint there
-// uses the same expressions, launch_bilinear_adjoint is this kernel's backward)
-template <typename T>
-__global__ __launch_bounds__(256) void bilinear_up_kernel(const void* in, void* out, int N, int H, int W, int vpc, int up, float sy, float sx) {
-  constexpr int VEC = EV<T>::VEC;
-  const int OH = H * up, OW = W * up;
-  const size_t nvec = (size_t)N * OH * OW * vpc;
-  for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += (size_t)gridDim.x * blockDim.x) {
-    const int cv = (int)(v % vpc);
-    size_t p = v / vpc;
-    const int ox = (int)(p % OW); p /= OW;
-    const int oy = (int)(p % OH);
-    const size_t n = p / OH;
-    const float fy = sy * (float)oy, fx = sx * (float)ox;
-    const int y0 = min((int)fy, H - 1), x0 = min((int)fx, W - 1);
-    const int y1 = y0 + (y0 < H - 1 ? 1 : 0), x1 = x0 + (x0 < W - 1 ? 1 : 0);
-    const float wy1 = fy - (float)y0, wy0 = 1.f - wy1, wx1 = fx - (float)x0, wx0 = 1.f - wx1;
-    float a00[VEC], a01[VEC], a10[VEC], a11[VEC], o[VEC];
-    EV<T>::unpack(ldv<T>(in, ((n * H + y0) * W + x0) * vpc + cv), a00);
-    EV<T>::unpack(ldv<T>(in, ((n * H + y0) * W + x1) * vpc + cv), a01);
-    EV<T>::unpack(ldv<T>(in, ((n * H + y1) * W + x0) * vpc + cv), a10);
-    EV<T>::unpack(ldv<T>(in, ((n * H + y1) * W + x1) * vpc + cv), a11);
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) o[i] = wy0 * (wx0 * a00[i] + wx1 * a01[i]) + wy1 * (wx0 * a10[i] + wx1 * a11[i]);
-    stv<T>(out, v, EV<T>::pack(o));
-  }
-}
+// (launch_bilinear_resize to H * up x W * up; fpn.hip's launch_bilinear_adjoint, built on the same index rule, is its backward)
 hipError_t launch_bilinear_up(int dtype, const void* in, void* out, int N, int H, int W, int C, int up, hipStream_t st) {
-  const int vec = dtype == DT_F32 ? 4 : 8;
-  if (C % vec != 0 || up < 2) return hipErrorInvalidValue;
-  const size_t nvec = (size_t)N * H * up * W * up * (C / vec);
-  const float sy = H * up > 1 ? (float)(H - 1) / (float)(H * up - 1) : 0.f, sx = W * up > 1 ? (float)(W - 1) / (float)(W * up - 1) : 0.f;
-  DL_DISPATCH(bilinear_up_kernel, dim3(grid_for(nvec, 256)), in, out, N, H, W, C / vec, up, sy, sx);
-  return hipGetLastError();
+  if (up < 2) return hipErrorInvalidValue;
+  return launch_bilinear_resize(dtype, in, out, N, H, W, H * up, W * up, C, st);
 }
 
 // ================================================================== PSPNet (smp decoders/pspnet, restated in oracle/nets.py PSPDecoder)
@@ -346,11 +308,11 @@ __global__ __launch_bounds__(256) void bin_mean_kernel(const void* in, void* out
   }
 }
 hipError_t launch_bin_mean(int dtype, const void* in, void* out, int N, int H, int W, int C, int k, hipStream_t st) {
-  const int vec = dtype == DT_F32 ? 4 : 8;
+  const int vec = ev_vec(dtype);
   if (C % vec != 0 || k < 1) return hipErrorInvalidValue;
   const int vpc = C / vec;
   const int ch = N * k * k >= 256 ? DW_CH : 8;      // the 1x1 / 2x2 bins of a 16-frame batch are 16 / 64 blocks of up to 7744 pixels each
-  DL_DISPATCH(bin_mean_kernel, dim3((vpc + ch - 1) / ch, N * k * k), in, out, H, W, k, vpc, ch);
+  OCTSEG_LAUNCH(bin_mean_kernel, dim3((vpc + ch - 1) / ch, N * k * k), dim3(256), in, out, H, W, k, vpc, ch);
   return hipGetLastError();
 }
 // its gradient, gather form: gin[n][y][x] (+)= sum over the bins that contain (y, x) of gout[bin] / area(bin)
@@ -387,25 +349,14 @@ __global__ __launch_bounds__(256) void bin_mean_bwd_kernel(const void* gout, voi
 }
 hipError_t launch_bin_mean_bwd(int dtype, const void* gout, void* gin, int N, int H, int W, int C, int k, int accum, hipStream_t st) {
   OCTSEG_NO_F16(dtype);
-  const int vec = dtype == DT_F32 ? 4 : 8;
+  const int vec = ev_vec(dtype);
   if (C % vec != 0 || k < 1) return hipErrorInvalidValue;
   const size_t nvec = (size_t)N * H * W * (C / vec);
-  if (dtype == DT_F32) hipLaunchKernelGGL(bin_mean_bwd_kernel<float>, dim3(grid_for(nvec, 256)), dim3(256), 0, st, gout, gin, N, H, W, k, C / vec, accum);
-  else hipLaunchKernelGGL(bin_mean_bwd_kernel<bf16_t>, dim3(grid_for(nvec, 256)), dim3(256), 0, st, gout, gin, N, H, W, k, C / vec, accum);
+  OCTSEG_LAUNCH_TRAIN(bin_mean_bwd_kernel, dim3(grid_for(nvec, 256)), dim3(256), gout, gin, N, H, W, k, C / vec, accum);
   return hipGetLastError();
 }
 
 // ------------------------------------------------------------------ F.interpolate(size=(OH, OW), mode='bilinear', align_corners=True), any size pair
-struct Tap2 { int i0, i1; float w0, w1; };
-static __device__ __forceinline__ Tap2 tap_of(int o, int in, float scale) {   // torch: x = scale * o, i0 = (int)x, lambda1 = x - i0
-  const float x = scale * (float)o;
-  Tap2 t;
-  t.i0 = min((int)x, in - 1);
-  t.i1 = t.i0 + (t.i0 < in - 1 ? 1 : 0);
-  t.w1 = x - (float)t.i0;
-  t.w0 = 1.f - t.w1;
-  return t;
-}
 template <typename T>
 __global__ __launch_bounds__(256) void bilinear_resize_kernel(const void* in, void* out, int N, int IH, int IW, int OH, int OW, int vpc, float sy, float sx) {
   constexpr int VEC = EV<T>::VEC;
@@ -416,7 +367,7 @@ __global__ __launch_bounds__(256) void bilinear_resize_kernel(const void* in, vo
     const int ox = (int)(p % OW); p /= OW;
     const int oy = (int)(p % OH);
     const size_t n = p / OH;
-    const Tap2 ty = tap_of(oy, IH, sy), tx = tap_of(ox, IW, sx);
+    const Lerp ty = lerp_of(oy, IH, sy), tx = lerp_of(ox, IW, sx);
     float a00[VEC], a01[VEC], a10[VEC], a11[VEC], o[VEC];
     EV<T>::unpack(ldv<T>(in, ((n * IH + ty.i0) * IW + tx.i0) * vpc + cv), a00);
     EV<T>::unpack(ldv<T>(in, ((n * IH + ty.i0) * IW + tx.i1) * vpc + cv), a01);
@@ -427,12 +378,11 @@ __global__ __launch_bounds__(256) void bilinear_resize_kernel(const void* in, vo
     stv<T>(out, v, EV<T>::pack(o));
   }
 }
-static inline float resize_scale(int in, int out) { return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f; }
 hipError_t launch_bilinear_resize(int dtype, const void* in, void* out, int N, int IH, int IW, int OH, int OW, int C, hipStream_t st) {
-  const int vec = dtype == DT_F32 ? 4 : 8;
+  const int vec = ev_vec(dtype);
   if (C % vec != 0) return hipErrorInvalidValue;
   const size_t nvec = (size_t)N * OH * OW * (C / vec);
-  DL_DISPATCH(bilinear_resize_kernel, dim3(grid_for(nvec, 256)), in, out, N, IH, IW, OH, OW, C / vec, resize_scale(IH, OH), resize_scale(IW, OW));
+  OCTSEG_LAUNCH(bilinear_resize_kernel, dim3(grid_for(nvec, 256)), dim3(256), in, out, N, IH, IW, OH, OW, C / vec, lerp_scale(IH, OH), lerp_scale(IW, OW));
   return hipGetLastError();
 }
 // adjoint, gather form (the source is a handful of pixels: k x k bins): one block per (image, source pixel, 32-vector channel chunk) walks
@@ -460,7 +410,7 @@ __global__ __launch_bounds__(256) void bilinear_resize_adjoint_kernel(const void
   if (r < rows)
     for (int q = r; q < cnt; q += rows) {
       const int oy = oy0 + q / bw, ox = ox0 + q % bw;
-      const Tap2 ty = tap_of(oy, IH, sy), tx = tap_of(ox, IW, sx);
+      const Lerp ty = lerp_of(oy, IH, sy), tx = lerp_of(ox, IW, sx);
       const float w = ((ty.i0 == iy ? ty.w0 : 0.f) + (ty.i1 == iy ? ty.w1 : 0.f)) * ((tx.i0 == ix ? tx.w0 : 0.f) + (tx.i1 == ix ? tx.w1 : 0.f));
       if (w == 0.f) continue;
       float f[VEC];
@@ -481,10 +431,10 @@ __global__ __launch_bounds__(256) void bilinear_resize_adjoint_kernel(const void
 }
 hipError_t launch_bilinear_resize_adjoint(int dtype, const void* gout, void* gin, int N, int IH, int IW, int OH, int OW, int C, hipStream_t st) {
   OCTSEG_NO_F16(dtype);
-  const int vec = dtype == DT_F32 ? 4 : 8;
+  const int vec = ev_vec(dtype);
   if (C % vec != 0) return hipErrorInvalidValue;
   const int vpc = C / vec;
-  const float sy = resize_scale(IH, OH), sx = resize_scale(IW, OW);
+  const float sy = lerp_scale(IH, OH), sx = lerp_scale(IW, OW);
   const long long npx = (long long)N * IH * IW;
   int gy = (int)npx, gz = 1;
   if (npx > 65535) {                       // one workgroup per source pixel: factor the count into grid.y x grid.z exactly
@@ -494,8 +444,7 @@ hipError_t launch_bilinear_resize_adjoint(int dtype, const void* gout, void* gin
     if (gz > 65535) return hipErrorInvalidValue;
   }
   const dim3 grid((vpc + DW_CH - 1) / DW_CH, gy, gz);
-  if (dtype == DT_F32) hipLaunchKernelGGL(bilinear_resize_adjoint_kernel<float>, grid, dim3(256), 0, st, gout, gin, IH, IW, OH, OW, vpc, sy, sx);
-  else hipLaunchKernelGGL(bilinear_resize_adjoint_kernel<bf16_t>, grid, dim3(256), 0, st, gout, gin, IH, IW, OH, OW, vpc, sy, sx);
+  OCTSEG_LAUNCH_TRAIN(bilinear_resize_adjoint_kernel, grid, dim3(256), gout, gin, IH, IW, OH, OW, vpc, sy, sx);
   return hipGetLastError();
 }
 
@@ -519,9 +468,9 @@ __global__ __launch_bounds__(256) void relu_kernel(const void* in, const void* m
   }
 }
 hipError_t launch_relu(int dtype, const void* in, const void* mask, void* out, size_t numel, hipStream_t st) {
-  const int vec = dtype == DT_F32 ? 4 : 8;
+  const int vec = ev_vec(dtype);
   if (numel % vec != 0) return hipErrorInvalidValue;
-  DL_DISPATCH(relu_kernel, dim3(grid_for(numel / vec, 256)), in, mask, out, numel / vec);
+  OCTSEG_LAUNCH(relu_kernel, dim3(grid_for(numel / vec, 256)), dim3(256), in, mask, out, numel / vec);
   return hipGetLastError();
 }
 
@@ -572,11 +521,11 @@ __global__ __launch_bounds__(256) void mosaic_kernel(const void* src, void* dst,
   }
 }
 hipError_t launch_mosaic(int dtype, const void* src, void* dst, int N, int H, int W, int C, int r, int to_mosaic, int accum, hipStream_t st) {
-  const int vec = dtype == DT_F32 ? 4 : 8;
+  const int vec = ev_vec(dtype);
   if (C % vec != 0 || r < 1) return hipErrorInvalidValue;
   const int hs = (H + r - 1) / r, ws = (W + r - 1) / r;
   const size_t nvec = to_mosaic ? (size_t)N * (r * (hs + 1) + 1) * (r * (ws + 1) + 1) * (C / vec) : (size_t)N * H * W * (C / vec);
-  DL_DISPATCH(mosaic_kernel, dim3(grid_for(nvec, 256)), src, dst, N, H, W, C / vec, r, hs, ws, to_mosaic, accum);
+  OCTSEG_LAUNCH(mosaic_kernel, dim3(grid_for(nvec, 256)), dim3(256), src, dst, N, H, W, C / vec, r, hs, ws, to_mosaic, accum);
   return hipGetLastError();
 }
 
@@ -612,13 +561,12 @@ __global__ __launch_bounds__(256) void tensor_stats_kernel(const void* y, size_t
 }
 hipError_t launch_tensor_stats(int dtype, const void* y, size_t npix, int C, float* slab, int rows, hipStream_t st) {
   OCTSEG_NO_F16(dtype);
-  const int vec = dtype == DT_F32 ? 4 : 8;
+  const int vec = ev_vec(dtype);
   if (C % vec != 0 || rows < 1) return hipErrorInvalidValue;
   const int vtot = C / vec;
   for (int cv0 = 0; cv0 < vtot; cv0 += 256) {      // wide tensors (RegNet stage 4: 1624 / 2240 channels) in chunks of 256 channel vectors
     const int vpc = vtot - cv0 < 256 ? vtot - cv0 : 256;
-    if (dtype == DT_F32) hipLaunchKernelGGL(tensor_stats_kernel<float>, dim3(rows), dim3(256), 0, st, y, npix, vpc, C, slab, vtot, cv0);
-    else hipLaunchKernelGGL(tensor_stats_kernel<bf16_t>, dim3(rows), dim3(256), 0, st, y, npix, vpc, C, slab, vtot, cv0);
+    OCTSEG_LAUNCH_TRAIN(tensor_stats_kernel, dim3(rows), dim3(256), y, npix, vpc, C, slab, vtot, cv0);
   }
   return hipGetLastError();
 }

@@ -12,35 +12,11 @@
 #include "common.h"
 #include "ev.h"
 #include "kernels.h"
+#include "sigmoid.h"
 
 #include <algorithm>
 
 namespace octseg {
-
-static __device__ __forceinline__ float ef_sigmoid(float z) {
-  const float e = expf(-fabsf(z));
-  return z >= 0.f ? 1.0f / (1.0f + e) : e / (1.0f + e);
-}
-template <typename T> static __device__ __forceinline__ float ef_ld1(const void* p, size_t i);
-template <> __device__ __forceinline__ float ef_ld1<float>(const void* p, size_t i) { return ((const float*)p)[i]; }
-template <> __device__ __forceinline__ float ef_ld1<bf16_t>(const void* p, size_t i) { return __uint_as_float((unsigned)((const unsigned short*)p)[i] << 16); }
-template <> __device__ __forceinline__ float ef_ld1<f16_t>(const void* p, size_t i) { return (float)__builtin_bit_cast(_Float16, ((const unsigned short*)p)[i]); }
-template <typename T> static __device__ __forceinline__ void ef_st1(void* p, size_t i, float v);
-template <> __device__ __forceinline__ void ef_st1<float>(void* p, size_t i, float v) { ((float*)p)[i] = v; }
-template <> __device__ __forceinline__ void ef_st1<bf16_t>(void* p, size_t i, float v) { ((unsigned short*)p)[i] = (unsigned short)(pk_bf16(v, 0.f) & 0xffffu); }
-template <> __device__ __forceinline__ void ef_st1<f16_t>(void* p, size_t i, float v) { const _Float16 h = (_Float16)v; ((unsigned short*)p)[i] = __builtin_bit_cast(unsigned short, h); }
-
-#define EF_DISPATCH(KERNEL, grid, ...)                                                          \
-  do {                                                                                          \
-    if (dtype == DT_F32) hipLaunchKernelGGL(KERNEL<float>, grid, dim3(256), 0, st, __VA_ARGS__);      \
-    else if (dtype == DT_F16) hipLaunchKernelGGL(KERNEL<f16_t>, grid, dim3(256), 0, st, __VA_ARGS__); \
-    else hipLaunchKernelGGL(KERNEL<bf16_t>, grid, dim3(256), 0, st, __VA_ARGS__);                     \
-  } while (0)
-#define EF_DISPATCH_TRAIN(KERNEL, grid, ...)                                                    \
-  do {                                                                                          \
-    if (dtype == DT_F32) hipLaunchKernelGGL(KERNEL<float>, grid, dim3(256), 0, st, __VA_ARGS__);      \
-    else hipLaunchKernelGGL(KERNEL<bf16_t>, grid, dim3(256), 0, st, __VA_ARGS__);                     \
-  } while (0)
 
 // ------------------------------------------------------------------ depthwise k x k, stride s, static "same" padding
 // out[n][oy][ox][c] = sum_{r,s} w[r][s][c] * in[n][oy * st - pt + r][ox * st - pt + s][c]     (zero outside the input)
@@ -176,31 +152,31 @@ __global__ __launch_bounds__(256) void dwg_bwd_w_kernel(const DwgArgs a) {
   }
 }
 static bool dwg_ok(int dtype, const DwgArgs& a) {
-  const int vec = dtype == DT_F32 ? 4 : 8;
+  const int vec = ev_vec(dtype);
   return a.C % vec == 0 && (a.K == 3 || a.K == 5) && (a.stride == 1 || a.stride == 2) && a.pad >= 0 && a.pad < a.K && a.OH >= 1 && a.OW >= 1 &&
          (a.OH - 1) * a.stride - a.pad < a.H && (a.OW - 1) * a.stride - a.pad < a.W;
 }
 hipError_t launch_dwg_fwd(int dtype, const DwgArgs& a, hipStream_t st) {
   if (!dwg_ok(dtype, a)) return hipErrorInvalidValue;
-  const size_t nvec = (size_t)a.N * a.OH * a.OW * (a.C / (dtype == DT_F32 ? 4 : 8));
-  EF_DISPATCH(dwg_fwd_kernel, dim3(grid_for(nvec, 256)), a);
+  const size_t nvec = (size_t)a.N * a.OH * a.OW * (a.C / ev_vec(dtype));
+  OCTSEG_LAUNCH(dwg_fwd_kernel, dim3(grid_for(nvec, 256)), dim3(256), a);
   return hipGetLastError();
 }
 hipError_t launch_dwg_bwd_data(int dtype, const DwgArgs& a, hipStream_t st) {
   OCTSEG_NO_F16(dtype);
   if (!dwg_ok(dtype, a)) return hipErrorInvalidValue;
-  const size_t nvec = (size_t)a.N * a.H * a.W * (a.C / (dtype == DT_F32 ? 4 : 8));
-  EF_DISPATCH_TRAIN(dwg_bwd_data_kernel, dim3(grid_for(nvec, 256)), a);
+  const size_t nvec = (size_t)a.N * a.H * a.W * (a.C / ev_vec(dtype));
+  OCTSEG_LAUNCH_TRAIN(dwg_bwd_data_kernel, dim3(grid_for(nvec, 256)), dim3(256), a);
   return hipGetLastError();
 }
 hipError_t launch_dwg_bwd_w(int dtype, const DwgArgs& a, hipStream_t st) {
   OCTSEG_NO_F16(dtype);
   if (!dwg_ok(dtype, a)) return hipErrorInvalidValue;
-  const int vpc = a.C / (dtype == DT_F32 ? 4 : 8);
+  const int vpc = a.C / ev_vec(dtype);
   const size_t npix = (size_t)a.N * a.OH * a.OW;
   int shares = deterministic_mode() ? 1 : (int)std::min<size_t>(256, (npix + 255) / 256);   // one writer per weight in deterministic mode
   if (shares < 1) shares = 1;
-  EF_DISPATCH_TRAIN(dwg_bwd_w_kernel, dim3((vpc + DWG_CH - 1) / DWG_CH, shares, a.K), a);
+  OCTSEG_LAUNCH_TRAIN(dwg_bwd_w_kernel, dim3((vpc + DWG_CH - 1) / DWG_CH, shares, a.K), dim3(256), a);
   return hipGetLastError();
 }
 
@@ -221,7 +197,7 @@ __global__ __launch_bounds__(256) void bnx_fwd_kernel(const BnxArgs a) {
     }
     if (a.act == 1) {
 #pragma unroll
-      for (int i = 0; i < VEC; ++i) x[i] = x[i] * ef_sigmoid(x[i]);
+      for (int i = 0; i < VEC; ++i) x[i] = x[i] * sigmoid_acc(x[i]);
     }
     if (a.dscale) {
       const float d = a.dscale[v / ((size_t)a.hw * vpc)];
@@ -258,7 +234,7 @@ __global__ __launch_bounds__(256) void bnx_bwd_kernel(const BnxArgs a) {
 #pragma unroll
       for (int i = 0; i < VEC; ++i) {
         const float z = fmaf(y[i], a.scale[c + i], a.shift[c + i]);
-        const float sg = ef_sigmoid(z);
+        const float sg = sigmoid_acc(z);
         g[i] *= sg * (1.0f + z * (1.0f - sg));     // d/dz z sigmoid(z)
       }
     }
@@ -274,16 +250,16 @@ static inline int ef_grid_for_channels(size_t nvec, int vpc) {   // the stride (
   return g < m ? m : g;
 }
 hipError_t launch_bnx_fwd(int dtype, const BnxArgs& a, hipStream_t st) {
-  const int vec = dtype == DT_F32 ? 4 : 8;
+  const int vec = ev_vec(dtype);
   if (a.C % vec != 0) return hipErrorInvalidValue;
-  EF_DISPATCH(bnx_fwd_kernel, dim3(grid_for(a.npix * (size_t)(a.C / vec), 256)), a);
+  OCTSEG_LAUNCH(bnx_fwd_kernel, dim3(grid_for(a.npix * (size_t)(a.C / vec), 256)), dim3(256), a);
   return hipGetLastError();
 }
 hipError_t launch_bnx_bwd(int dtype, const BnxArgs& a, hipStream_t st) {
   OCTSEG_NO_F16(dtype);
-  const int vec = dtype == DT_F32 ? 4 : 8;
+  const int vec = ev_vec(dtype);
   if (a.C % vec != 0) return hipErrorInvalidValue;
-  EF_DISPATCH_TRAIN(bnx_bwd_kernel, dim3(grid_for(a.npix * (size_t)(a.C / vec), 256)), a);
+  OCTSEG_LAUNCH_TRAIN(bnx_bwd_kernel, dim3(grid_for(a.npix * (size_t)(a.C / vec), 256)), dim3(256), a);
   return hipGetLastError();
 }
 
@@ -294,21 +270,21 @@ __global__ __launch_bounds__(256) void sefc_fwd_kernel(const SefcArgs a) {
   extern __shared__ float sm[];            // m [C], act [R]
   float* m = sm; float* act = sm + a.C;
   const size_t n = blockIdx.x;
-  for (int c = threadIdx.x; c < a.C; c += 256) m[c] = ef_ld1<T>(a.m, n * a.C + c);
+  for (int c = threadIdx.x; c < a.C; c += 256) m[c] = ld1<T>(a.m, n * a.C + c);
   __syncthreads();
   for (int j = threadIdx.x; j < a.R; j += 256) {
     float h = a.b1[j];
     const float* w = a.w1 + (size_t)j * a.C;
     for (int c = 0; c < a.C; ++c) h = fmaf(w[c], m[c], h);
     a.h[n * a.R + j] = h;
-    act[j] = a.act ? h * ef_sigmoid(h) : fmaxf(h, 0.f);
+    act[j] = a.act ? h * sigmoid_acc(h) : fmaxf(h, 0.f);
   }
   __syncthreads();
   for (int c = threadIdx.x; c < a.C; c += 256) {
     float s = a.b2[c];
     const float* w = a.w2 + (size_t)c * a.R;
     for (int j = 0; j < a.R; ++j) s = fmaf(w[j], act[j], s);
-    ef_st1<T>(a.s, n * a.C + c, s);
+    st1<T>(a.s, n * a.C + c, s);
   }
 }
 // per image: dh[n][j] = swish'(h) * sum_c W2[c][j] ds[n][c] (kept, float);  dm[n][c] = sum_j W1[j][c] dh[n][j]
@@ -317,12 +293,12 @@ __global__ __launch_bounds__(256) void sefc_bwd_kernel(const SefcArgs a) {
   extern __shared__ float sm[];            // ds [C], dh [R]
   float* ds = sm; float* dh = sm + a.C;
   const size_t n = blockIdx.x;
-  for (int c = threadIdx.x; c < a.C; c += 256) ds[c] = ef_ld1<T>(a.ds, n * a.C + c);
+  for (int c = threadIdx.x; c < a.C; c += 256) ds[c] = ld1<T>(a.ds, n * a.C + c);
   __syncthreads();
   for (int j = threadIdx.x; j < a.R; j += 256) {
     float d = 0.f;
     for (int c = 0; c < a.C; ++c) d = fmaf(a.w2[(size_t)c * a.R + j], ds[c], d);
-    const float h = a.h[n * a.R + j], sg = ef_sigmoid(h);
+    const float h = a.h[n * a.R + j], sg = sigmoid_acc(h);
     d *= a.act ? sg * (1.0f + h * (1.0f - sg)) : (h > 0.f ? 1.f : 0.f);
     dh[j] = d;
     a.dh[n * a.R + j] = d;
@@ -331,7 +307,7 @@ __global__ __launch_bounds__(256) void sefc_bwd_kernel(const SefcArgs a) {
   for (int c = threadIdx.x; c < a.C; c += 256) {
     float d = 0.f;
     for (int j = 0; j < a.R; ++j) d = fmaf(a.w1[(size_t)j * a.C + c], dh[j], d);
-    ef_st1<T>(a.dm, n * a.C + c, d);
+    st1<T>(a.dm, n * a.C + c, d);
   }
 }
 // weight gradients, one thread per element, images summed in order (deterministic):
@@ -346,16 +322,16 @@ __global__ __launch_bounds__(256) void sefc_wgrad_kernel(const SefcArgs a) {
       const int c = e / a.R, j = e - c * a.R;
       for (int n = 0; n < a.N; ++n) {
         const float h = a.h[(size_t)n * a.R + j];
-        acc = fmaf(ef_ld1<T>(a.ds, (size_t)n * a.C + c), a.act ? h * ef_sigmoid(h) : fmaxf(h, 0.f), acc);
+        acc = fmaf(ld1<T>(a.ds, (size_t)n * a.C + c), a.act ? h * sigmoid_acc(h) : fmaxf(h, 0.f), acc);
       }
       a.dw2[e] += acc;
     } else if (e < 2 * CR) {            // dW1[j][c]
       const int k = e - CR, j = k / a.C, c = k - j * a.C;
-      for (int n = 0; n < a.N; ++n) acc = fmaf(a.dh[(size_t)n * a.R + j], ef_ld1<T>(a.m, (size_t)n * a.C + c), acc);
+      for (int n = 0; n < a.N; ++n) acc = fmaf(a.dh[(size_t)n * a.R + j], ld1<T>(a.m, (size_t)n * a.C + c), acc);
       a.dw1[k] += acc;
     } else if (e < 2 * CR + a.C) {      // db2[c]
       const int c = e - 2 * CR;
-      for (int n = 0; n < a.N; ++n) acc += ef_ld1<T>(a.ds, (size_t)n * a.C + c);
+      for (int n = 0; n < a.N; ++n) acc += ld1<T>(a.ds, (size_t)n * a.C + c);
       a.db2[c] += acc;
     } else {                            // db1[j]
       const int j = e - 2 * CR - a.C;
@@ -367,21 +343,17 @@ __global__ __launch_bounds__(256) void sefc_wgrad_kernel(const SefcArgs a) {
 hipError_t launch_sefc_fwd(int dtype, const SefcArgs& a, hipStream_t st) {
   const size_t lds = (size_t)(a.C + a.R) * sizeof(float);
   if (lds > 60 * 1024 || a.R < 1) return hipErrorInvalidValue;
-  if (dtype == DT_F32) hipLaunchKernelGGL(sefc_fwd_kernel<float>, dim3(a.N), dim3(256), lds, st, a);
-  else if (dtype == DT_F16) hipLaunchKernelGGL(sefc_fwd_kernel<f16_t>, dim3(a.N), dim3(256), lds, st, a);
-  else hipLaunchKernelGGL(sefc_fwd_kernel<bf16_t>, dim3(a.N), dim3(256), lds, st, a);
+  OCTSEG_LAUNCH_LDS(sefc_fwd_kernel, dim3(a.N), dim3(256), lds, a);
   return hipGetLastError();
 }
 hipError_t launch_sefc_bwd(int dtype, const SefcArgs& a, hipStream_t st) {
   OCTSEG_NO_F16(dtype);
   const size_t lds = (size_t)(a.C + a.R) * sizeof(float);
   if (lds > 60 * 1024 || a.R < 1) return hipErrorInvalidValue;
-  if (dtype == DT_F32) hipLaunchKernelGGL(sefc_bwd_kernel<float>, dim3(a.N), dim3(256), lds, st, a);
-  else hipLaunchKernelGGL(sefc_bwd_kernel<bf16_t>, dim3(a.N), dim3(256), lds, st, a);
+  OCTSEG_LAUNCH_TRAIN_LDS(sefc_bwd_kernel, dim3(a.N), dim3(256), lds, a);
   if (a.dw1 == nullptr) return hipGetLastError();   // data-only backward: no parameter gradient wanted
   const int total = 2 * a.C * a.R + a.C + a.R;
-  if (dtype == DT_F32) hipLaunchKernelGGL(sefc_wgrad_kernel<float>, dim3(grid_for((size_t)total, 256)), dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(sefc_wgrad_kernel<bf16_t>, dim3(grid_for((size_t)total, 256)), dim3(256), 0, st, a);
+  OCTSEG_LAUNCH_TRAIN(sefc_wgrad_kernel, dim3(grid_for((size_t)total, 256)), dim3(256), a);
   return hipGetLastError();
 }
 

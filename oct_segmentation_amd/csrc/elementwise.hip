@@ -195,8 +195,7 @@ hipError_t launch_bn_finalize_small(int dtype, const void* y, int count, int C, 
                                     hipStream_t st) {
   OCTSEG_NO_F16(dtype);
   const dim3 grid((C + 31) / 32);
-  if (dtype == DT_F32) hipLaunchKernelGGL(bn_finalize_small_kernel<float>, grid, dim3(1024), 0, st, y, count, C, gamma, beta, running_mean, running_var, momentum, eps, scale, shift, mean, rstd);
-  else hipLaunchKernelGGL(bn_finalize_small_kernel<bf16_t>, grid, dim3(1024), 0, st, y, count, C, gamma, beta, running_mean, running_var, momentum, eps, scale, shift, mean, rstd);
+  OCTSEG_LAUNCH_TRAIN(bn_finalize_small_kernel, grid, dim3(1024), y, count, C, gamma, beta, running_mean, running_var, momentum, eps, scale, shift, mean, rstd);
   return hipGetLastError();
 }
 
@@ -319,7 +318,7 @@ static inline int grid_for_channels(size_t nvec, int vpc) {
   return g < m ? m : g;
 }
 hipError_t launch_bn_act(int dtype, const BnActArgs& a, hipStream_t st) {
-  const int vpc = a.C / (dtype == DT_F32 ? 4 : 8);
+  const int vpc = a.C / ev_vec(dtype);
   const size_t nvec = a.npix * (size_t)vpc;
   const int g = grid_for_channels(nvec, vpc);
   if (dtype == DT_F16) hipLaunchKernelGGL(bn_act_kernel<f16_t>, dim3(g), dim3(256), 0, st, a);
@@ -382,11 +381,10 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const BnBwdArgs a) {
 }
 hipError_t launch_bn_bwd_reduce(int dtype, const BnBwdArgs& a, hipStream_t st) {
   OCTSEG_NO_F16(dtype);
-  const int VEC = dtype == DT_F32 ? 4 : 8;
+  const int VEC = ev_vec(dtype);
   const int vpc = a.C / VEC;
   dim3 grid(a.rows, vpc >= 256 ? vpc / 256 : 1);
-  if (dtype == DT_F32) hipLaunchKernelGGL(bn_bwd_reduce_kernel<float>, grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(bn_bwd_reduce_kernel<bf16_t>, grid, dim3(256), 0, st, a);
+  OCTSEG_LAUNCH_TRAIN(bn_bwd_reduce_kernel, grid, dim3(256), a);
   return hipGetLastError();
 }
 
@@ -456,8 +454,7 @@ __global__ __launch_bounds__(1024) void bn_bwd_small_kernel(const BnBwdArgs a) {
 hipError_t launch_bn_bwd_small(int dtype, const BnBwdArgs& a, hipStream_t st) {
   OCTSEG_NO_F16(dtype);
   const dim3 grid((a.C + 31) / 32);
-  if (dtype == DT_F32) hipLaunchKernelGGL(bn_bwd_small_kernel<float>, grid, dim3(1024), 0, st, a);
-  else hipLaunchKernelGGL(bn_bwd_small_kernel<bf16_t>, grid, dim3(1024), 0, st, a);
+  OCTSEG_LAUNCH_TRAIN(bn_bwd_small_kernel, grid, dim3(1024), a);
   return hipGetLastError();
 }
 
@@ -554,7 +551,7 @@ __global__ __launch_bounds__(256, 4) void bn_bwd_apply_kernel(const BnBwdArgs a)
 }
 hipError_t launch_bn_bwd_apply(int dtype, const BnBwdArgs& a, hipStream_t st) {
   OCTSEG_NO_F16(dtype);
-  const int vpc = a.C / (dtype == DT_F32 ? 4 : 8);
+  const int vpc = a.C / ev_vec(dtype);
   const size_t nvec = a.npix * (size_t)vpc;
   const int g = grid_for_channels(nvec, vpc);
   const int mm = a.mask == 2 ? (a.maskbits != nullptr ? 3 : 2) : a.mask;
@@ -594,10 +591,9 @@ __global__ __launch_bounds__(256) void masked_accum_kernel(void* dst, const void
 }
 hipError_t launch_masked_accum(int dtype, void* dst, const void* g, const void* out_mask, size_t n, int store, hipStream_t st) {
   OCTSEG_NO_F16(dtype);
-  const size_t nvec = n / (dtype == DT_F32 ? 4 : 8);
+  const size_t nvec = n / ev_vec(dtype);
   const int gr = grid_for(nvec, 256);
-  if (dtype == DT_F32) hipLaunchKernelGGL(masked_accum_kernel<float>, dim3(gr), dim3(256), 0, st, dst, g, out_mask, nvec, store);
-  else hipLaunchKernelGGL(masked_accum_kernel<bf16_t>, dim3(gr), dim3(256), 0, st, dst, g, out_mask, nvec, store);
+  OCTSEG_LAUNCH_TRAIN(masked_accum_kernel, dim3(gr), dim3(256), dst, g, out_mask, nvec, store);
   return hipGetLastError();
 }
 
@@ -634,10 +630,9 @@ __global__ __launch_bounds__(256) void pool2x2_accum_kernel(void* dst, const voi
 }
 hipError_t launch_pool2x2_accum(int dtype, void* dst, const void* src, int N, int H, int W, int C, int store, hipStream_t st) {
   OCTSEG_NO_F16(dtype);
-  const size_t nvec = (size_t)N * H * W * (C / (dtype == DT_F32 ? 4 : 8));
+  const size_t nvec = (size_t)N * H * W * (C / ev_vec(dtype));
   const int gr = grid_for(nvec, 256);
-  if (dtype == DT_F32) hipLaunchKernelGGL(pool2x2_accum_kernel<float>, dim3(gr), dim3(256), 0, st, dst, src, N, H, W, C, store);
-  else hipLaunchKernelGGL(pool2x2_accum_kernel<bf16_t>, dim3(gr), dim3(256), 0, st, dst, src, N, H, W, C, store);
+  OCTSEG_LAUNCH_TRAIN(pool2x2_accum_kernel, dim3(gr), dim3(256), dst, src, N, H, W, C, store);
   return hipGetLastError();
 }
 
@@ -698,19 +693,17 @@ __global__ __launch_bounds__(256) void channel_sum_vec_kernel(const void* g, siz
 }
 hipError_t launch_channel_sum(int dtype, const void* g, size_t npix, int Cstride, int C, float* out, hipStream_t st) {
   OCTSEG_NO_F16(dtype);
-  const int vw = dtype == DT_F32 ? 4 : 8;
+  const int vw = ev_vec(dtype);
   if (C % vw == 0 && Cstride % vw == 0 && C / vw <= 256 && ((uintptr_t)g & 15) == 0) {
     const int nvc = C / vw, rows = 256 / nvc;
     size_t want = (npix + (size_t)rows * 8 - 1) / ((size_t)rows * 8);
     const int gr = deterministic_mode() ? 1 : (int)(want < 1 ? 1 : want > 1024 ? 1024 : want);
     const size_t lds = (size_t)rows * C * sizeof(float);
-    if (dtype == DT_F32) hipLaunchKernelGGL(channel_sum_vec_kernel<float>, dim3(gr), dim3(256), lds, st, g, npix, Cstride, C, rows, out);
-    else hipLaunchKernelGGL(channel_sum_vec_kernel<bf16_t>, dim3(gr), dim3(256), lds, st, g, npix, Cstride, C, rows, out);
+    OCTSEG_LAUNCH_TRAIN_LDS(channel_sum_vec_kernel, dim3(gr), dim3(256), lds, g, npix, Cstride, C, rows, out);
     return hipGetLastError();
   }
   const int gr = deterministic_mode() ? 1 : grid_for(npix, 256, 512);
-  if (dtype == DT_F32) hipLaunchKernelGGL(channel_sum_kernel<float>, dim3(gr), dim3(256), 0, st, g, npix, Cstride, C, out);
-  else hipLaunchKernelGGL(channel_sum_kernel<bf16_t>, dim3(gr), dim3(256), 0, st, g, npix, Cstride, C, out);
+  OCTSEG_LAUNCH_TRAIN(channel_sum_kernel, dim3(gr), dim3(256), g, npix, Cstride, C, out);
   return hipGetLastError();
 }
 
@@ -751,7 +744,7 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const void* in, void* 
   }
 }
 hipError_t launch_maxpool_fwd(int dtype, const void* in, void* out, unsigned char* idx, int N, int H, int W, int C, hipStream_t st) {
-  const size_t nvec = (size_t)N * (H / 2) * (W / 2) * (C / (dtype == DT_F32 ? 4 : 8));
+  const size_t nvec = (size_t)N * (H / 2) * (W / 2) * (C / ev_vec(dtype));
   const int gr = grid_for(nvec, 256);
   if (dtype == DT_F16) hipLaunchKernelGGL(maxpool_fwd_kernel<f16_t>, dim3(gr), dim3(256), 0, st, in, out, idx, N, H, W, C);
   else if (dtype == DT_F32) hipLaunchKernelGGL(maxpool_fwd_kernel<float>, dim3(gr), dim3(256), 0, st, in, out, idx, N, H, W, C);
@@ -807,10 +800,9 @@ __global__ __launch_bounds__(256) void maxpool_bwd_idx_kernel(const unsigned cha
 hipError_t launch_maxpool_bwd_idx(int dtype, const unsigned char* idx, const void* gout, void* gin, int N, int H, int W, int C, int store,
                                   hipStream_t st) {
   OCTSEG_NO_F16(dtype);
-  const size_t nvec = (size_t)N * H * W * (C / (dtype == DT_F32 ? 4 : 8));
+  const size_t nvec = (size_t)N * H * W * (C / ev_vec(dtype));
   const int gr = grid_for(nvec, 256);
-  if (dtype == DT_F32) hipLaunchKernelGGL(maxpool_bwd_idx_kernel<float>, dim3(gr), dim3(256), 0, st, idx, gout, gin, N, H, W, C, store);
-  else hipLaunchKernelGGL(maxpool_bwd_idx_kernel<bf16_t>, dim3(gr), dim3(256), 0, st, idx, gout, gin, N, H, W, C, store);
+  OCTSEG_LAUNCH_TRAIN(maxpool_bwd_idx_kernel, dim3(gr), dim3(256), idx, gout, gin, N, H, W, C, store);
   return hipGetLastError();
 }
 
@@ -850,7 +842,7 @@ __global__ __launch_bounds__(256) void stem_im2col_kernel(const float* img, void
 hipError_t launch_stem_im2col(int dtype, const float* img, void* col, int N, int H, int W, int KP,
                               const float* mean, const float* stdv, int normalize, hipStream_t st, int ksize, int pad) {
   if (pad < 0) pad = ksize / 2;
-  const size_t nvec = (size_t)N * (H / 2) * (W / 2) * (KP / (dtype == DT_F32 ? 4 : 8));
+  const size_t nvec = (size_t)N * (H / 2) * (W / 2) * (KP / ev_vec(dtype));
   const int gr = grid_for(nvec, 256);
   float m[3] = {0, 0, 0}, iv[3] = {1, 1, 1};
   if (normalize) for (int i = 0; i < 3; ++i) { m[i] = mean[i]; iv[i] = 1.0f / stdv[i]; }
@@ -864,7 +856,6 @@ hipError_t launch_stem_im2col(int dtype, const float* img, void* col, int N, int
 }
 
 // ------------------------------------------------------------------ Dice loss
-static __device__ __forceinline__ float sigmoid_f(float z) { return 1.0f / (1.0f + __expf(-z)); }
 // sigmoid_acc: sigmoid.h (shared with panels.hip)
 template <typename V> static __device__ __forceinline__ V block_sum(V v, V* red) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
@@ -1009,8 +1000,7 @@ hipError_t launch_dice_bwd(int dtype, const DiceArgs& a, float grad_scale, void*
   if (a.C > CP || CP > 16 || CP % 8 != 0) return hipErrorInvalidValue;
   const size_t npix = (size_t)a.B * a.HW;
   const int gr = grid_for(npix, 256);
-  if (dtype == DT_F32) hipLaunchKernelGGL(dice_bwd_kernel<float>, dim3(gr), dim3(256), 0, st, a, grad_scale, dlogits, CP);
-  else hipLaunchKernelGGL(dice_bwd_kernel<bf16_t>, dim3(gr), dim3(256), 0, st, a, grad_scale, dlogits, CP);
+  OCTSEG_LAUNCH_TRAIN(dice_bwd_kernel, dim3(gr), dim3(256), a, grad_scale, dlogits, CP);
   return hipGetLastError();
 }
 

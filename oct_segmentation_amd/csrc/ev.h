@@ -1,5 +1,6 @@
-// ev.h -- 16-byte element-vector helpers shared by the HBM-bound kernels (elementwise.hip, fpn.hip): NHWC tensors are moved as
-// 8 x bf16 / f16 or 4 x f32 per lane and processed in f32.
+// ev.h -- what every HBM-bound NHWC sweep kernel shares: the 16-byte element vectors (tensors are moved as 8 x bf16 / f16 or 4 x f32 per
+// lane and processed in f32), scalar element access, the dtype dispatch of a launch, the grid rule, and torch's align_corners=True
+// source-index rule.  A dtype is added, or a conversion changed, here and nowhere else.
 #pragma once
 #include "common.h"
 
@@ -48,6 +49,33 @@ template <> struct EV<f16_t> {   // IEEE half (serving dtype): conversions round
     return make_uint4(w[0], w[1], w[2], w[3]);
   }
 };
+// one element (the kernels whose channel counts do not fill a vector)
+template <typename T> static __device__ __forceinline__ float ld1(const void* p, size_t i);
+template <> __device__ __forceinline__ float ld1<float>(const void* p, size_t i) { return ((const float*)p)[i]; }
+template <> __device__ __forceinline__ float ld1<bf16_t>(const void* p, size_t i) { return __uint_as_float((unsigned)((const unsigned short*)p)[i] << 16); }
+template <> __device__ __forceinline__ float ld1<f16_t>(const void* p, size_t i) { return (float)__builtin_bit_cast(_Float16, ((const unsigned short*)p)[i]); }
+template <typename T> static __device__ __forceinline__ void st1(void* p, size_t i, float v);
+template <> __device__ __forceinline__ void st1<float>(void* p, size_t i, float v) { ((float*)p)[i] = v; }
+template <> __device__ __forceinline__ void st1<bf16_t>(void* p, size_t i, float v) { ((unsigned short*)p)[i] = (unsigned short)(pk_bf16(v, 0.f) & 0xffffu); }
+template <> __device__ __forceinline__ void st1<f16_t>(void* p, size_t i, float v) { const _Float16 h = (_Float16)v; ((unsigned short*)p)[i] = __builtin_bit_cast(unsigned short, h); }
+
+static inline int ev_vec(int dtype) { return dtype == DT_F32 ? 4 : 8; }   // elements of one 16-byte vector (EV<T>::VEC, on the host)
+
+// KERNEL<T> for the `dtype` and on the stream `st` of the enclosing launcher.  OCTSEG_LAUNCH: every dtype.  OCTSEG_LAUNCH_TRAIN: kernels
+// with no f16 instantiation (the training-only sweeps, and pure 16-byte moves): f32 -> float, everything else -> bf16_t.
+#define OCTSEG_LAUNCH_LDS(KERNEL, grid, block, lds, ...)                                        \
+  do {                                                                                          \
+    if (dtype == DT_F32) hipLaunchKernelGGL(KERNEL<float>, grid, block, lds, st, __VA_ARGS__);      \
+    else if (dtype == DT_F16) hipLaunchKernelGGL(KERNEL<f16_t>, grid, block, lds, st, __VA_ARGS__); \
+    else hipLaunchKernelGGL(KERNEL<bf16_t>, grid, block, lds, st, __VA_ARGS__);                     \
+  } while (0)
+#define OCTSEG_LAUNCH_TRAIN_LDS(KERNEL, grid, block, lds, ...)                                  \
+  do {                                                                                          \
+    if (dtype == DT_F32) hipLaunchKernelGGL(KERNEL<float>, grid, block, lds, st, __VA_ARGS__);      \
+    else hipLaunchKernelGGL(KERNEL<bf16_t>, grid, block, lds, st, __VA_ARGS__);                     \
+  } while (0)
+#define OCTSEG_LAUNCH(KERNEL, grid, block, ...) OCTSEG_LAUNCH_LDS(KERNEL, grid, block, 0, __VA_ARGS__)
+#define OCTSEG_LAUNCH_TRAIN(KERNEL, grid, block, ...) OCTSEG_LAUNCH_TRAIN_LDS(KERNEL, grid, block, 0, __VA_ARGS__)
 // f16 is the dtype of eval forwards only: the training-only sweeps have no f16 instantiation and refuse it
 #define OCTSEG_NO_F16(dtype) do { if ((dtype) == DT_F16) return hipErrorInvalidValue; } while (0)
 template <typename T> static __device__ __forceinline__ uint4 ldv(const void* p, size_t vec_idx) {
@@ -63,5 +91,19 @@ static inline int grid_for(size_t n, int block, int cap = 8192) {
   if (g < 1) g = 1;
   return (int)g;
 }
+
+
+// torch's align_corners=True source index: scale = (in - 1) / (out - 1) in float, x = scale * o, i0 = (int)x, lambda1 = x - i0
+struct Lerp { int i0, i1; float w0, w1; };
+static __device__ __forceinline__ Lerp lerp_of(int o, int in, float scale) {
+  const float x = scale * (float)o;
+  Lerp l;
+  l.i0 = min((int)x, in - 1);
+  l.i1 = l.i0 + (l.i0 < in - 1 ? 1 : 0);
+  l.w1 = x - (float)l.i0;
+  l.w0 = 1.f - l.w1;
+  return l;
+}
+static inline float lerp_scale(int in, int out) { return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f; }
 
 }  // namespace octseg

@@ -12,19 +12,6 @@
 
 namespace octseg {
 
-// torch's align_corners=True source index: scale = (in - 1) / (out - 1) in float, x = scale * o, i0 = (int)x, lambda1 = x - i0
-struct Lerp { int i0, i1; float w0, w1; };
-static __device__ __forceinline__ Lerp lerp_of(int o, int in, float scale) {
-  const float x = scale * (float)o;
-  Lerp l;
-  l.i0 = min((int)x, in - 1);
-  l.i1 = l.i0 + (l.i0 < in - 1 ? 1 : 0);
-  l.w1 = x - (float)l.i0;
-  l.w0 = 1.f - l.w1;
-  return l;
-}
-static inline float lerp_scale(int in, int out) { return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f; }
-
 // ------------------------------------------------------------------ nearest x2 fill (FPNBlock: x = interpolate(x, 2, 'nearest'); the skip conv then accumulates)
 template <typename T>
 __global__ __launch_bounds__(256) void up2_fill_kernel(const void* in, void* out, int N, int H, int W, int vpc) {
@@ -39,11 +26,10 @@ __global__ __launch_bounds__(256) void up2_fill_kernel(const void* in, void* out
   }
 }
 hipError_t launch_up2_fill(int dtype, const void* in, void* out, int N, int H, int W, int C, hipStream_t st) {
-  const int vpc = C / (dtype == DT_F32 ? 4 : 8);
+  const int vpc = C / ev_vec(dtype);
   const size_t nvec = (size_t)N * 4 * H * W * vpc;
   const int g = grid_for(nvec, 256);
-  if (dtype == DT_F32) hipLaunchKernelGGL(up2_fill_kernel<float>, dim3(g), dim3(256), 0, st, in, out, N, H, W, vpc);
-  else hipLaunchKernelGGL(up2_fill_kernel<bf16_t>, dim3(g), dim3(256), 0, st, in, out, N, H, W, vpc);   // (16-byte moves: any 2-byte type)
+  OCTSEG_LAUNCH_TRAIN(up2_fill_kernel, dim3(g), dim3(256), in, out, N, H, W, vpc);   // (16-byte moves: any 2-byte type)
   return hipGetLastError();
 }
 
@@ -326,15 +312,8 @@ __global__ __launch_bounds__(256) void bilinear_nchw_kernel(const float* z, floa
 static inline int gn_slabs(size_t HW) { size_t s = HW / 1024; return s < 1 ? 1 : (s > 64 ? 64 : (int)s); }
 int gn_num_slabs(size_t HW) { return gn_slabs(HW); }
 
-#define FPN_DISPATCH(KERNEL, grid, ...)                                                        \
-  do {                                                                                          \
-    if (dtype == DT_F32) hipLaunchKernelGGL(KERNEL<float>, grid, dim3(256), 0, st, __VA_ARGS__);      \
-    else if (dtype == DT_F16) hipLaunchKernelGGL(KERNEL<f16_t>, grid, dim3(256), 0, st, __VA_ARGS__); \
-    else hipLaunchKernelGGL(KERNEL<bf16_t>, grid, dim3(256), 0, st, __VA_ARGS__);                     \
-  } while (0)
-
 static bool gn_shape_ok(int dtype, const GnArgs& a) {
-  const int vec = dtype == DT_F32 ? 4 : 8;
+  const int vec = ev_vec(dtype);
   const int vpc = a.C / vec;
   return a.C % vec == 0 && a.C <= 1024 && vpc >= 1 && vpc <= 256 && 256 % vpc == 0 && a.C % a.G == 0 && a.cpg == a.C / a.G;
 }
@@ -347,8 +326,8 @@ hipError_t launch_gn_forward(int dtype, const GnArgs& a, int N, int H, int W, in
   else if (dtype == DT_F16) hipLaunchKernelGGL((gn_reduce_kernel<f16_t, 0>), dim3(S, N), dim3(256), 0, st, a);
   else hipLaunchKernelGGL((gn_reduce_kernel<bf16_t, 0>), dim3(S, N), dim3(256), 0, st, a);
   hipLaunchKernelGGL(gn_finalize_kernel, dim3(N), dim3(1024), 0, st, a, S);
-  const size_t nvec = (size_t)N * H * W * up * up * (a.C / (dtype == DT_F32 ? 4 : 8));
-  FPN_DISPATCH(gn_act_up_kernel, dim3(grid_for(nvec, 256)), a, N, H, W, up, lerp_scale(H, H * up), lerp_scale(W, W * up));
+  const size_t nvec = (size_t)N * H * W * up * up * (a.C / ev_vec(dtype));
+  OCTSEG_LAUNCH(gn_act_up_kernel, dim3(grid_for(nvec, 256)), dim3(256), a, N, H, W, up, lerp_scale(H, H * up), lerp_scale(W, W * up));
   return hipGetLastError();
 }
 // backward: a.g holds d/d(relu(gn(y))) at the resolution of y (the caller has applied the resample's adjoint); a.dy may alias a.g
@@ -358,29 +337,27 @@ hipError_t launch_gn_backward(int dtype, const GnArgs& a, int N, hipStream_t st)
   if (dtype == DT_F32) hipLaunchKernelGGL((gn_reduce_kernel<float, 1>), dim3(S, N), dim3(256), 0, st, a);
   else hipLaunchKernelGGL((gn_reduce_kernel<bf16_t, 1>), dim3(S, N), dim3(256), 0, st, a);
   hipLaunchKernelGGL(gn_bwd_finalize_kernel, dim3(1), dim3(1024), 0, st, a, S, N);
-  const size_t nvec = (size_t)N * a.HW * (a.C / (dtype == DT_F32 ? 4 : 8));
-  if (dtype == DT_F32) hipLaunchKernelGGL(gn_bwd_apply_kernel<float>, dim3(grid_for(nvec, 256)), dim3(256), 0, st, a, N);
-  else hipLaunchKernelGGL(gn_bwd_apply_kernel<bf16_t>, dim3(grid_for(nvec, 256)), dim3(256), 0, st, a, N);
+  const size_t nvec = (size_t)N * a.HW * (a.C / ev_vec(dtype));
+  OCTSEG_LAUNCH_TRAIN(gn_bwd_apply_kernel, dim3(grid_for(nvec, 256)), dim3(256), a, N);
   return hipGetLastError();
 }
 hipError_t launch_bilinear_adjoint(int dtype, const void* gout, void* gin, int N, int H, int W, int C, int up, hipStream_t st) {
-  if (dtype == DT_F16 || C % (dtype == DT_F32 ? 4 : 8) != 0 || up < 2) return hipErrorInvalidValue;
-  const size_t nvec = (size_t)N * H * W * (C / (dtype == DT_F32 ? 4 : 8));
+  if (dtype == DT_F16 || C % ev_vec(dtype) != 0 || up < 2) return hipErrorInvalidValue;
+  const size_t nvec = (size_t)N * H * W * (C / ev_vec(dtype));
   const float sy = lerp_scale(H, H * up), sx = lerp_scale(W, W * up);
   const float isy = sy > 0.f ? 1.f / sy : 0.f, isx = sx > 0.f ? 1.f / sx : 0.f;
-  if (dtype == DT_F32) hipLaunchKernelGGL(bilinear_adjoint_kernel<float>, dim3(grid_for(nvec, 256)), dim3(256), 0, st, gout, gin, N, H, W, C, up, sy, sx, isy, isx);
-  else hipLaunchKernelGGL(bilinear_adjoint_kernel<bf16_t>, dim3(grid_for(nvec, 256)), dim3(256), 0, st, gout, gin, N, H, W, C, up, sy, sx, isy, isx);
+  OCTSEG_LAUNCH_TRAIN(bilinear_adjoint_kernel, dim3(grid_for(nvec, 256)), dim3(256), gout, gin, N, H, W, C, up, sy, sx, isy, isx);
   return hipGetLastError();
 }
 hipError_t launch_merge_drop(int dtype, const void* a0, const void* a1, const void* a2, const void* a3, const float* m, float mscale, void* out,
                              int N, size_t HW, int C, hipStream_t st) {
-  const size_t nvec = (size_t)N * HW * (C / (dtype == DT_F32 ? 4 : 8));
-  FPN_DISPATCH(merge_drop_kernel, dim3(grid_for(nvec, 256)), a0, a1, a2, a3, m, mscale, out, HW, C, nvec);
+  const size_t nvec = (size_t)N * HW * (C / ev_vec(dtype));
+  OCTSEG_LAUNCH(merge_drop_kernel, dim3(grid_for(nvec, 256)), dim3(256), a0, a1, a2, a3, m, mscale, out, HW, C, nvec);
   return hipGetLastError();
 }
 hipError_t launch_drop_bwd(int dtype, const void* gout, const float* m, float mscale, void* gin, int N, size_t HW, int C, hipStream_t st) {
-  const size_t nvec = (size_t)N * HW * (C / (dtype == DT_F32 ? 4 : 8));
-  FPN_DISPATCH(drop_bwd_kernel, dim3(grid_for(nvec, 256)), gout, m, mscale, gin, HW, C, nvec);
+  const size_t nvec = (size_t)N * HW * (C / ev_vec(dtype));
+  OCTSEG_LAUNCH(drop_bwd_kernel, dim3(grid_for(nvec, 256)), dim3(256), gout, m, mscale, gin, HW, C, nvec);
   return hipGetLastError();
 }
 hipError_t launch_bilinear_nchw(const float* z, float* out, int NC, int H, int W, int up, hipStream_t st) {

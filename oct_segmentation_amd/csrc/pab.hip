@@ -14,25 +14,14 @@
 
 namespace octseg {
 
+// an operand is of the tensor dtype T, or f32 scratch (is_f32)
 template <typename T> static __device__ __forceinline__ float pab_ld(const void* p, size_t i, int is_f32) {
-  if (is_f32 || sizeof(T) == 4) return ((const float*)p)[i];
-  if (sizeof(T) == 2 && T::kHalf) return (float)__builtin_bit_cast(_Float16, ((const unsigned short*)p)[i]);
-  return __uint_as_float((unsigned)((const unsigned short*)p)[i] << 16);
+  return is_f32 ? ld1<float>(p, i) : ld1<T>(p, i);
 }
 template <typename T> static __device__ __forceinline__ void pab_st(void* p, size_t i, float v, int is_f32, int accum) {
-  if (is_f32 || sizeof(T) == 4) { float* q = (float*)p + i; *q = accum ? *q + v : v; return; }
-  unsigned short* q = (unsigned short*)p + i;
-  if (T::kHalf) {
-    if (accum) v += (float)__builtin_bit_cast(_Float16, *q);
-    const _Float16 h = (_Float16)v; *q = __builtin_bit_cast(unsigned short, h);
-  } else {
-    if (accum) v += __uint_as_float((unsigned)*q << 16);
-    *q = (unsigned short)(pk_bf16(v, 0.f) & 0xffffu);
-  }
+  if (is_f32) st1<float>(p, i, accum ? ld1<float>(p, i) + v : v);
+  else st1<T>(p, i, accum ? ld1<T>(p, i) + v : v);
 }
-struct PabF32 { static constexpr bool kHalf = false; float x; };
-struct PabBf16 { static constexpr bool kHalf = false; unsigned short x; };
-struct PabF16 { static constexpr bool kHalf = true; unsigned short x; };
 
 // C[b][m][n] (+)= sum_k A[b][m][k] B[b][k][n], element (m, k) of A at sAm m + sAk k (likewise B, C); 16 x 16 tiles through LDS
 template <typename T>
@@ -60,9 +49,7 @@ __global__ __launch_bounds__(256) void pab_gemm_kernel(const PabGemm g) {
 }
 hipError_t launch_pab_gemm(int dtype, const PabGemm& g, hipStream_t st) {
   const dim3 grid((g.N + 15) / 16, (g.M + 15) / 16, g.batch);
-  if (dtype == DT_F32) hipLaunchKernelGGL(pab_gemm_kernel<PabF32>, grid, dim3(256), 0, st, g);
-  else if (dtype == DT_F16) hipLaunchKernelGGL(pab_gemm_kernel<PabF16>, grid, dim3(256), 0, st, g);
-  else hipLaunchKernelGGL(pab_gemm_kernel<PabBf16>, grid, dim3(256), 0, st, g);
+  OCTSEG_LAUNCH(pab_gemm_kernel, grid, dim3(256), g);
   return hipGetLastError();
 }
 
@@ -119,9 +106,7 @@ __global__ __launch_bounds__(256) void pab_mix_kernel(const void* x, const float
 hipError_t launch_pab_mix(int dtype, const void* x, const float* M, void* y, float* dM, const void* dy, int N, int HW, int C, hipStream_t st) {
   const size_t total = (size_t)N * HW * C;
   const dim3 grid(grid_for(total, 256));
-  if (dtype == DT_F32) hipLaunchKernelGGL(pab_mix_kernel<PabF32>, grid, dim3(256), 0, st, x, M, y, dM, dy, HW, C, total);
-  else if (dtype == DT_F16) hipLaunchKernelGGL(pab_mix_kernel<PabF16>, grid, dim3(256), 0, st, x, M, y, dM, dy, HW, C, total);
-  else hipLaunchKernelGGL(pab_mix_kernel<PabBf16>, grid, dim3(256), 0, st, x, M, y, dM, dy, HW, C, total);
+  OCTSEG_LAUNCH(pab_mix_kernel, grid, dim3(256), x, M, y, dM, dy, HW, C, total);
   return hipGetLastError();
 }
 

@@ -15,24 +15,6 @@
 
 namespace octseg {
 
-template <typename T> static __device__ __forceinline__ float pn_ld(const void* p, size_t i) {
-  if (sizeof(T) == 4) return ((const float*)p)[i];
-  return __uint_as_float((unsigned)((const unsigned short*)p)[i] << 16);
-}
-template <> __device__ __forceinline__ float pn_ld<f16_t>(const void* p, size_t i) { return (float)__builtin_bit_cast(_Float16, ((const unsigned short*)p)[i]); }
-template <typename T> static __device__ __forceinline__ void pn_st(void* p, size_t i, float v) {
-  if (sizeof(T) == 4) ((float*)p)[i] = v;
-  else ((unsigned short*)p)[i] = (unsigned short)(pk_bf16(v, 0.f) & 0xffffu);
-}
-template <> __device__ __forceinline__ void pn_st<f16_t>(void* p, size_t i, float v) { const _Float16 h = (_Float16)v; ((unsigned short*)p)[i] = __builtin_bit_cast(unsigned short, h); }
-
-#define PN_DISPATCH(KERNEL, grid, block, ...)                                                          \
-  do {                                                                                                 \
-    if (dtype == DT_F32) hipLaunchKernelGGL(KERNEL<float>, grid, block, 0, st, __VA_ARGS__);      \
-    else if (dtype == DT_F16) hipLaunchKernelGGL(KERNEL<f16_t>, grid, block, 0, st, __VA_ARGS__); \
-    else hipLaunchKernelGGL(KERNEL<bf16_t>, grid, block, 0, st, __VA_ARGS__);                     \
-  } while (0)
-
 // ------------------------------------------------------------------ MaxPool2d(2, 2) on NHWC vectors, and its gradient (first maximum in scan order, as torch)
 template <typename T>
 __global__ __launch_bounds__(256) void maxpool2_kernel(const void* x, void* p, const void* dp, void* dx, int H, int W, int vpc, size_t nvec, int accum) {
@@ -73,10 +55,10 @@ __global__ __launch_bounds__(256) void maxpool2_kernel(const void* x, void* p, c
   }
 }
 hipError_t launch_maxpool2(int dtype, const void* x, void* p, const void* dp, void* dx, int N, int H, int W, int C, int accum, hipStream_t st) {
-  const int vec = dtype == DT_F32 ? 4 : 8;
+  const int vec = ev_vec(dtype);
   if (C % vec != 0 || (H & 1) || (W & 1)) return hipErrorInvalidValue;
   const size_t nvec = (size_t)N * (H / 2) * (W / 2) * (C / vec);
-  PN_DISPATCH(maxpool2_kernel, dim3(grid_for(nvec, 256)), dim3(256), x, p, dp, dx, H, W, C / vec, nvec, accum);
+  OCTSEG_LAUNCH(maxpool2_kernel, dim3(grid_for(nvec, 256)), dim3(256), x, p, dp, dx, H, W, C / vec, nvec, accum);
   return hipGetLastError();
 }
 
@@ -94,7 +76,7 @@ __global__ __launch_bounds__(256) void fpa_in_fwd_kernel(const void* p, const fl
     if ((unsigned)iy >= (unsigned)H || (unsigned)ix >= (unsigned)W) continue;
     const size_t base = ((n * H + iy) * W + ix) * C;
     float a = 0.f;
-    for (int c = threadIdx.x; c < C; c += 256) a = fmaf(w[(size_t)t * C + c], pn_ld<T>(p, base + c), a);
+    for (int c = threadIdx.x; c < C; c += 256) a = fmaf(w[(size_t)t * C + c], ld1<T>(p, base + c), a);
     acc += (double)a;
   }
   red[threadIdx.x] = acc;
@@ -117,7 +99,7 @@ __global__ __launch_bounds__(256) void fpa_in_bwd_x_kernel(const float* dy, cons
       if ((unsigned)oy >= (unsigned)H || (unsigned)ox >= (unsigned)W) continue;
       acc = fmaf(w[(size_t)t * C + c], dy[(n * H + oy) * W + ox], acc);
     }
-    pn_st<T>(dp, e, acc);
+    st1<T>(dp, e, acc);
   }
 }
 // dw[t][c] += sum_{n,oy,ox} dy[n][oy][ox] p[n][oy + r - K/2][ox + s - K/2][c]: grid (ceil(C / 256), K * K); db += sum dy (block (0, 0))
@@ -134,7 +116,7 @@ __global__ __launch_bounds__(256) void fpa_in_bwd_w_kernel(const void* p, const 
         for (int ox = 0; ox < W; ++ox) {
           const int ix = ox + ds;
           if ((unsigned)ix >= (unsigned)W) continue;
-          acc = fmaf(dy[((size_t)n * H + oy) * W + ox], pn_ld<T>(p, (((size_t)n * H + iy) * W + ix) * C + c), acc);
+          acc = fmaf(dy[((size_t)n * H + oy) * W + ox], ld1<T>(p, (((size_t)n * H + iy) * W + ix) * C + c), acc);
         }
       }
     dw[(size_t)t * C + c] += acc;
@@ -146,7 +128,7 @@ __global__ __launch_bounds__(256) void fpa_in_bwd_w_kernel(const void* p, const 
   }
 }
 hipError_t launch_fpa_in_fwd(int dtype, const void* p, const float* w, const float* b, float* y, int N, int H, int W, int C, int K, hipStream_t st) {
-  PN_DISPATCH(fpa_in_fwd_kernel, dim3((unsigned)((size_t)N * H * W)), dim3(256), p, w, b, y, H, W, C, K);
+  OCTSEG_LAUNCH(fpa_in_fwd_kernel, dim3((unsigned)((size_t)N * H * W)), dim3(256), p, w, b, y, H, W, C, K);
   return hipGetLastError();
 }
 hipError_t launch_fpa_in_bwd(int dtype, const void* p, const float* dy, const float* w, void* dp, float* dw, float* db, int N, int H, int W, int C, int K,
@@ -435,13 +417,13 @@ __global__ __launch_bounds__(256) void fpa_mix_kernel(const float* uu, const voi
     const size_t n = p / HW;
     const float u = uu[p];
     if (g == nullptr) {
-      for (int c = 0; c < C; ++c) pn_st<T>(out, p * C + c, fmaf(u, pn_ld<T>(mid, p * C + c), pn_ld<T>(b1, n * C + c)));
+      for (int c = 0; c < C; ++c) st1<T>(out, p * C + c, fmaf(u, ld1<T>(mid, p * C + c), ld1<T>(b1, n * C + c)));
     } else {
       float s = 0.f;
       for (int c = 0; c < C; ++c) {
-        const float gv = pn_ld<T>(g, p * C + c);
-        s = fmaf(gv, pn_ld<T>(mid, p * C + c), s);
-        pn_st<T>(dmid, p * C + c, gv * u);
+        const float gv = ld1<T>(g, p * C + c);
+        s = fmaf(gv, ld1<T>(mid, p * C + c), s);
+        st1<T>(dmid, p * C + c, gv * u);
       }
       duu[p] = s;
     }
@@ -450,7 +432,7 @@ __global__ __launch_bounds__(256) void fpa_mix_kernel(const float* uu, const voi
 hipError_t launch_fpa_mix(int dtype, const float* uu, const void* mid, const void* b1, void* out, const void* g, void* dmid, float* duu, int N, int HW, int C,
                           hipStream_t st) {
   const size_t npix = (size_t)N * HW;
-  PN_DISPATCH(fpa_mix_kernel, dim3(grid_for(npix, 256)), dim3(256), uu, mid, b1, out, g, dmid, duu, HW, C, npix);
+  OCTSEG_LAUNCH(fpa_mix_kernel, dim3(grid_for(npix, 256)), dim3(256), uu, mid, b1, out, g, dmid, duu, HW, C, npix);
   return hipGetLastError();
 }
 
@@ -468,9 +450,9 @@ __global__ __launch_bounds__(256) void add2_kernel(const void* a, const void* b,
   }
 }
 hipError_t launch_add2(int dtype, const void* a, const void* b, void* out, size_t numel, hipStream_t st) {
-  const int vec = dtype == DT_F32 ? 4 : 8;
+  const int vec = ev_vec(dtype);
   if (numel % vec != 0) return hipErrorInvalidValue;
-  PN_DISPATCH(add2_kernel, dim3(grid_for(numel / vec, 256)), dim3(256), a, b, out, numel / vec);
+  OCTSEG_LAUNCH(add2_kernel, dim3(grid_for(numel / vec, 256)), dim3(256), a, b, out, numel / vec);
   return hipGetLastError();
 }
 

@@ -26,7 +26,7 @@ static int bn_backward(Exec& E, int bn, const void* g, int mask, const void* out
   a.npix = (size_t)t.N * t.H * t.W; a.C = b.C; a.mask = mask;
   a.slab = (float*)(E.ws + P->slab_off);
   a.part = (double*)(E.ws + P->fin_part_off); a.counters = (unsigned*)(E.ws + P->fin_cnt_off);
-  const int VEC = P->dtype == DT_F32 ? 4 : 8;
+  const int VEC = ev_vec(P->dtype);
   const int vpc = b.C / VEC;
   const int tpv = vpc >= 256 ? 1 : 256 / vpc;
   size_t rows = (a.npix + tpv - 1) / tpv;

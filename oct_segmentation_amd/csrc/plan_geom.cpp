@@ -178,7 +178,7 @@ double layer_macs(const ConvLayer& L) {
 
 // ---------------------------------------------------------------- single-op entry points (octseg_conv2d_*): what they accept, and its Geom
 bool geom_ok(int dtype, int Cin, int Cout, int R, int S, int stride, int transposed) {
-  const int v = dtype == OCTSEG_F32 ? 4 : 8;
+  const int v = ev_vec(dtype);
   (void)Cout;
   if (Cin % v != 0) return false;
   if (R != S || R < 1 || R > 7) return false;

@@ -3,6 +3,7 @@
 // state named here is defined in exactly one .cpp.
 #pragma once
 #include "plan.h"
+#include "ev.h"
 
 #include <algorithm>
 #include <cstdint>

@@ -11,20 +11,9 @@
 #include "common.h"
 #include "ev.h"
 #include "kernels.h"
+#include "sigmoid.h"
 
 namespace octseg {
-
-#define SE_DISPATCH(KERNEL, grid, ...)                                                          \
-  do {                                                                                          \
-    if (dtype == DT_F32) hipLaunchKernelGGL(KERNEL<float>, grid, dim3(256), 0, st, __VA_ARGS__);      \
-    else if (dtype == DT_F16) hipLaunchKernelGGL(KERNEL<f16_t>, grid, dim3(256), 0, st, __VA_ARGS__); \
-    else hipLaunchKernelGGL(KERNEL<bf16_t>, grid, dim3(256), 0, st, __VA_ARGS__);                     \
-  } while (0)
-
-static __device__ __forceinline__ float se_sigmoid(float z) {
-  const float e = expf(-fabsf(z));                    // (no overflow for large |z|)
-  return z >= 0.f ? 1.0f / (1.0f + e) : e / (1.0f + e);
-}
 
 // out (+)= in * sigmoid(s[n][c])
 template <typename T>
@@ -37,12 +26,12 @@ __global__ __launch_bounds__(256) void se_gate_kernel(const void* in, const void
     EV<T>::unpack(ldv<T>(in, v), f);
     EV<T>::unpack(ldv<T>(s, n * vpc + cv), g);
 #pragma unroll
-    for (int i = 0; i < VEC; ++i) g[i] = se_sigmoid(g[i]);
+    for (int i = 0; i < VEC; ++i) g[i] = sigmoid_acc(g[i]);
     if (s2 != nullptr) {       // MAnet's MFAB: attention_hl + attention_ll, each behind its own sigmoid
       float g2[VEC];
       EV<T>::unpack(ldv<T>(s2, n * vpc + cv), g2);
 #pragma unroll
-      for (int i = 0; i < VEC; ++i) g[i] += se_sigmoid(g2[i]);
+      for (int i = 0; i < VEC; ++i) g[i] += sigmoid_acc(g2[i]);
     }
 #pragma unroll
     for (int i = 0; i < VEC; ++i) f[i] *= g[i];
@@ -56,10 +45,10 @@ __global__ __launch_bounds__(256) void se_gate_kernel(const void* in, const void
   }
 }
 hipError_t launch_se_gate(int dtype, const void* in, const void* s, void* out, int N, int HW, int C, int accum, hipStream_t st, const void* s2) {
-  const int vec = dtype == DT_F32 ? 4 : 8;
+  const int vec = ev_vec(dtype);
   if (C % vec != 0) return hipErrorInvalidValue;
   const size_t nvec = (size_t)N * HW * (C / vec);
-  SE_DISPATCH(se_gate_kernel, dim3(grid_for(nvec, 256)), in, s, out, (size_t)HW, C / vec, accum, nvec, s2);
+  OCTSEG_LAUNCH(se_gate_kernel, dim3(grid_for(nvec, 256)), dim3(256), in, s, out, (size_t)HW, C / vec, accum, nvec, s2);
   return hipGetLastError();
 }
 
@@ -114,12 +103,12 @@ __global__ __launch_bounds__(256) void se_dgate_fin_kernel(const float* part, co
     EV<T>::unpack(ldv<T>(s, v), z);
     float o[VEC];
 #pragma unroll
-    for (int i = 0; i < VEC; ++i) { const float q = se_sigmoid(z[i]); o[i] = acc[i] * q * (1.0f - q); }
+    for (int i = 0; i < VEC; ++i) { const float q = sigmoid_acc(z[i]); o[i] = acc[i] * q * (1.0f - q); }
     stv<T>(ds, v, EV<T>::pack(o));
     if (s2 != nullptr) {       // the second excitation of a two-gate sum sees the same sum of g * x
       EV<T>::unpack(ldv<T>(s2, v), z);
 #pragma unroll
-      for (int i = 0; i < VEC; ++i) { const float q = se_sigmoid(z[i]); o[i] = acc[i] * q * (1.0f - q); }
+      for (int i = 0; i < VEC; ++i) { const float q = sigmoid_acc(z[i]); o[i] = acc[i] * q * (1.0f - q); }
       stv<T>(ds2, v, EV<T>::pack(o));
     }
   }
@@ -131,14 +120,12 @@ int se_dgate_shares(int HW) {        // pixel shares of the s-side reduction: >=
 hipError_t launch_se_dgate(int dtype, const void* g, const void* x, const void* s, void* ds, float* part, int N, int HW, int C, hipStream_t st,
                            const void* s2, void* ds2) {
   OCTSEG_NO_F16(dtype);
-  const int vec = dtype == DT_F32 ? 4 : 8;
+  const int vec = ev_vec(dtype);
   if (C % vec != 0) return hipErrorInvalidValue;
   const int vpc = C / vec, shares = se_dgate_shares(HW);
-  if (dtype == DT_F32) hipLaunchKernelGGL(se_dgate_part_kernel<float>, dim3((vpc + SE_CH - 1) / SE_CH, shares, N), dim3(256), 0, st, g, x, part, HW, vpc);
-  else hipLaunchKernelGGL(se_dgate_part_kernel<bf16_t>, dim3((vpc + SE_CH - 1) / SE_CH, shares, N), dim3(256), 0, st, g, x, part, HW, vpc);
+  OCTSEG_LAUNCH_TRAIN(se_dgate_part_kernel, dim3((vpc + SE_CH - 1) / SE_CH, shares, N), dim3(256), g, x, part, HW, vpc);
   const int nvec = N * vpc;
-  if (dtype == DT_F32) hipLaunchKernelGGL(se_dgate_fin_kernel<float>, dim3(grid_for((size_t)nvec, 256)), dim3(256), 0, st, part, s, ds, shares, vpc, nvec, s2, ds2);
-  else hipLaunchKernelGGL(se_dgate_fin_kernel<bf16_t>, dim3(grid_for((size_t)nvec, 256)), dim3(256), 0, st, part, s, ds, shares, vpc, nvec, s2, ds2);
+  OCTSEG_LAUNCH_TRAIN(se_dgate_fin_kernel, dim3(grid_for((size_t)nvec, 256)), dim3(256), part, s, ds, shares, vpc, nvec, s2, ds2);
   return hipGetLastError();
 }
 
