@@ -37,6 +37,9 @@
  *                                      maps (src/models/smp/model.py:208-271, called from on_validation_epoch_end, model.py:134-148)
  *   octseg_stack_measure               the measurements of the app's get_analysis: set pixels per slice and class, and the ray walk of
  *                                      calculate_object_thickness per slice, class and degree (src/app/tools/analysis.py:60-130,189,199-200)
+ *   octseg_stack_polar / octseg_frames_unwrap
+ *                                      (no reference counterpart) the rays of calculate_object_thickness walked to their end: first entry, first
+ *                                      exit, last set step, set steps and runs per slice, class and degree; the polar label map and frame view
  *   octseg_stack_components / octseg_stack_cleanup / octseg_components_scratch_bytes
  *                                      MaskProcessor.smooth_mask / .remove_artifacts, which process_pair runs over every annotated object
  *                                      (src/data/mask_processor.py:5-37, src/data/convert_int_to_cv.py:191-199)
@@ -290,6 +293,31 @@ int octseg_epoch_panels(const float* frames, const float* logits, const uint8_t*
  * H * W >= 2^31: OCTSEG_BAD_SHAPE. */
 int octseg_stack_measure(const float* stack, int N, int H, int W, int stack_channels, const int* ray_pix, const int* ray_len, int R, int* counts,
                          int* radii, void* stream);
+
+/* The polar plaque profile: the rays of calculate_object_thickness (reference src/app/tools/analysis.py:60-130; the rays from the frame centre
+ * are the A-lines of a catheter-centred frame) walked to their END.  The reference's walk -- and radii of octseg_stack_measure -- stops at
+ * the first exit, which for anything but the lumen is the distance of the object's far edge, not its thickness; no reference counterpart
+ * states where an object begins on the ray or what lies behind it.  stack, ray_pix, ray_len, R: as for octseg_stack_measure, but
+ * stack_channels <= 8 (the label map keeps one bit per class in a byte).  With len = min(max(ray_len[angle], 0), R) and
+ * v[r] = stack[n][ray_pix[angle][r - 1]][c] != 0 for r = 1 .. len, prof: int32 [N][stack_channels][360][5] =
+ *   0 IN    the first r with v[r]; 0 if none (steps start at 1);
+ *   1 OUT   g - 1 for the first clear step g > IN; len if the run reaches the ray's end; 0 if none.  By definition the value
+ *           octseg_stack_measure writes to radii;
+ *   2 LAST  the last r with v[r]; 0 if none;
+ *   3 HITS  the number of r with v[r];
+ *   4 RUNS  the number of maximal runs of set steps.
+ * map (may be NULL): uint8 [N][360][R], entry [n][angle][r - 1] has bit c set iff class c is set at step r; entries past ray_len[angle] are
+ * written as 0, so the caller need not clear the buffer.  R == 0 (a 1 x 1 frame): the profiles are zero and the map has no entries.
+ * octseg_frames_unwrap: the same table as a nearest gather of uint8 frames [N][H][W][channels], channels = 1 or 3, into out uint8
+ * [N][360][R][channels], zeros past ray_len[angle]: the polar view of the frame that the label map lines up with.
+ * Integer results, no tolerance.  The host mirror (oct_segmentation_amd/polar.py) turns prof into arcs, thicknesses and the cap-over-lipid
+ * report.  Enqueue only (one launch each; none for octseg_frames_unwrap with R == 0).  Null pointer (ray_pix may be null only with R == 0),
+ * N, H, W, stack_channels <= 0, stack_channels > 8, channels not 1 / 3, R < 0 or H * W >= 2^31: OCTSEG_BAD_ARG.  Nothing is launched and no
+ * output is touched then. */
+int octseg_stack_polar(const float* stack, int N, int H, int W, int stack_channels, const int* ray_pix, const int* ray_len, int R,
+                       int* prof, unsigned char* map /* may be NULL */, void* stream);
+int octseg_frames_unwrap(const unsigned char* frames, int N, int H, int W, int channels, const int* ray_pix, const int* ray_len, int R,
+                         unsigned char* out, void* stream);
 
 /* Mask clean-up (reference src/data/mask_processor.py:5-37: MaskProcessor.smooth_mask and .remove_artifacts, run by process_pair,
  * src/data/convert_int_to_cv.py:191-199), on connected components by pixel count (DESIGN.md section 5g states how that differs from

@@ -88,6 +88,9 @@ SYMBOLS = {
     'octseg_epoch_panels': (C.c_int, [_P, _P, _P] + [C.c_int] * 6 + [_P] * 8),
     # float32 mask stack + host ray table -> int32 set-pixel counts and per-degree radii (csrc/measure.hip)
     'octseg_stack_measure': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P]),
+    # float32 mask stack + the same ray table -> int32 polar profile [N, C, 360, 5] (+ uint8 label map); uint8 frames -> polar view (csrc/polar.hip)
+    'octseg_stack_polar': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P]),
+    'octseg_frames_unwrap': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P]),
     # float32 mask stack -> connected components (labels, count, the 8 largest) and the cleaned stack: smooth, keep-largest, hole fill
     # (csrc/components.hip)
     'octseg_components_scratch_bytes': (C.c_size_t, [C.c_int] * 3),

@@ -293,6 +293,31 @@ int octseg_stack_measure(const float* stack, int N, int H, int W, int stack_chan
   return OCTSEG_OK;
 }
 
+// The polar plaque profile over the rays of calculate_object_thickness (app/tools/analysis.py:60-130): see polar.hip.  Enqueue only.
+static int polar_args(const char* who, const void* in, int N, int H, int W, const int* ray_pix, const int* ray_len, int R, const void* out) {
+  if (!in || !ray_len || !out || (!ray_pix && R != 0)) return fail(OCTSEG_BAD_ARG, std::string(who) + ": null argument");
+  if (N <= 0 || H <= 0 || W <= 0) return fail(OCTSEG_BAD_ARG, std::string(who) + ": empty batch or frame");
+  if (R < 0) return fail(OCTSEG_BAD_ARG, std::string(who) + ": negative ray table length");
+  if ((long long)H * W >= (1ll << 31)) return fail(OCTSEG_BAD_ARG, std::string(who) + ": H * W must be below 2^31");
+  return OCTSEG_OK;
+}
+
+int octseg_stack_polar(const float* stack, int N, int H, int W, int stack_channels, const int* ray_pix, const int* ray_len, int R, int* prof,
+                       unsigned char* map, void* stream) {
+  if (const int rc = polar_args("stack_polar", stack, N, H, W, ray_pix, ray_len, R, prof)) return rc;
+  if (stack_channels <= 0 || stack_channels > 8) return fail(OCTSEG_BAD_ARG, "stack_polar: 1..8 channels (the label map keeps a bit per class in a byte)");
+  HIPCHK(launch_stack_polar(stack, N, H, W, stack_channels, ray_pix, ray_len, R, prof, map, (hipStream_t)stream));
+  return OCTSEG_OK;
+}
+
+int octseg_frames_unwrap(const unsigned char* frames, int N, int H, int W, int channels, const int* ray_pix, const int* ray_len, int R,
+                         unsigned char* out, void* stream) {
+  if (const int rc = polar_args("frames_unwrap", frames, N, H, W, ray_pix, ray_len, R, out)) return rc;
+  if (channels != 1 && channels != 3) return fail(OCTSEG_BAD_ARG, "frames_unwrap: 1 or 3 channels");
+  HIPCHK(launch_frames_unwrap(frames, N, H, W, channels, ray_pix, ray_len, R, out, (hipStream_t)stream));
+  return OCTSEG_OK;
+}
+
 // Mask clean-up (data/mask_processor.py:5-37, run by process_pair, data/convert_int_to_cv.py:191-199): see components.hip.  Enqueue only.
 static int components_args(const char* who, const void* stack, int N, int H, int W, int channels, const void* scratch, size_t scratch_bytes) {
   if (!stack || !scratch) return fail(OCTSEG_BAD_ARG, "null argument");

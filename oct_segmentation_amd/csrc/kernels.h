@@ -325,6 +325,14 @@ hipError_t launch_epoch_panels(const float* frames, const float* logits, const u
 hipError_t launch_stack_measure(const float* stack, int N, int H, int W, int SC, const int* ray_pix, const int* ray_len, int R, int* counts,
                                 int* radii, hipStream_t st);
 
+// the polar plaque profile (polar.hip): the same ray walk carried to the end of every ray -- first entry, first exit, last set step, set steps and
+// runs per slice, channel (at most 8) and degree, optionally the label map [N][360][R] with a bit per channel; one launch.  launch_frames_unwrap:
+// the table as a nearest gather of uint8 frames [N][H][W][C], C = 1 | 3, into [N][360][R][C], zeros past the ray's end; one launch (none when R == 0)
+hipError_t launch_stack_polar(const float* stack, int N, int H, int W, int SC, const int* ray_pix, const int* ray_len, int R, int* prof,
+                              uint8_t* map, hipStream_t st);
+hipError_t launch_frames_unwrap(const uint8_t* frames, int N, int H, int W, int C, const int* ray_pix, const int* ray_len, int R, uint8_t* out,
+                                hipStream_t st);
+
 // mask clean-up (components.hip): connected components of every (slice, channel) plane by union-find on bit planes, the 8 largest with their
 // bounding boxes, keep-largest / min-area filter, hole fill (the same labelling on the complement, 4-connected) and the reference's
 // smooth_mask chain.  scratch: components_scratch_bytes(N * C, H, W) device bytes; labels / ncomp / top are optional (null = skipped)

@@ -278,7 +278,7 @@ def _main_volume(cfg, device, dtypes, log):
     res = analyze_pullback(volume, str(cfg['models_dir']), cfg['classes'], output_size=cfg['output_size'], names=names, render=True,
                            close_iterations=int(cfg.get('close_iterations', 1)), device=device, batch_size=int(cfg.get('batch_size', 8)),
                            compute_dtype=dtypes[str(cfg.get('compute_dtype', 'bf16'))], use_graph=bool(cfg.get('use_graph', False)),
-                           clean=bool(cfg.get('clean', False)))
+                           clean=bool(cfg.get('clean', False)), plaque=bool(cfg.get('plaque', False)))
     out = torch.stack([res.overlay, res.color_mask]).cpu().numpy()
     save_dir = str(cfg['save_dir'])
     for i, name in enumerate(names):
@@ -287,6 +287,17 @@ def _main_volume(cfg, device, dtypes, log):
     if bool(cfg.get('analysis', False)):
         with open(os.path.join(save_dir, 'analysis.json'), 'w') as f:
             json.dump(res.data, f)
+    if res.plaque is not None:
+        _save_plaque(res.plaque, res.stack, cfg['classes'], save_dir)
+
+
+def _save_plaque(report, stack, classes, save_dir):
+    """``plaque=true``: ``{save_dir}/plaque.json`` (``polar.plaque_report``) and ``plaque_carpet.png`` (``polar.carpet_view``: rows are degrees,
+    columns the slices in the report's order)."""
+    from .polar import carpet_view, polar_profile
+    with open(os.path.join(save_dir, 'plaque.json'), 'w') as f:
+        json.dump(report, f)
+    Image.fromarray(carpet_view(polar_profile(stack), classes)).save(os.path.join(save_dir, 'plaque_carpet.png'))
 
 
 def _image_paths(data_path):
@@ -306,6 +317,8 @@ def main(argv=None):
     (``analysis.analyze_stack``), with the frames as the slices of one pullback in sorted file-name order, as the app sorts its mask files;
     ``clean`` (default false): the mask stack goes through ``cleanup.clean_stack`` (the reference's ``MaskProcessor``: smoothing, the three
     largest components, hole fill) before it is rendered and measured;
+    ``plaque`` (default false): also write ``{save_dir}/plaque.json``, the polar plaque report of the same stack (``polar.plaque_report``: lipid
+    arc, cap thickness where lipid lies behind it), and ``plaque_carpet.png`` (``polar.carpet_view``), slices in the order ``analysis`` uses;
     ``device_resize`` (default true): ``RGB`` and ``L`` files go up at source size and ``data_processing``'s ``Image.resize`` runs on the GPU
     (``pullback.resize_pil_u8``, byte-identical; false restores the host resize for every file).  A ``data_dir`` that is a ``.npy`` file is a
     raw volume (a DICOM's ``pixel_array``) and goes through ``pullback.analyze_pullback``: see ``_main_volume``."""
@@ -354,6 +367,11 @@ def main(argv=None):
         data = analyze_stack(stack[torch.tensor(order, device=stack.device)], [names[i] for i in order])
         with open(os.path.join(str(cfg['save_dir']), 'analysis.json'), 'w') as f:
             json.dump(data, f)
+    if bool(cfg.get('plaque', False)):
+        from .polar import plaque_report
+        order = sorted(range(len(paths)), key=lambda i: os.path.basename(paths[i]))
+        ordered = stack[torch.tensor(order, device=stack.device)]
+        _save_plaque(plaque_report(ordered, [names[i] for i in order]), ordered, cfg['classes'], str(cfg['save_dir']))
     log.info(f'Overall computation time: {time.time() - start:.1f} s')
     log.info('Complete')
     return 0

@@ -27,7 +27,7 @@ BICUBIC_SUPPORT = 2.0
 
 _tables = {}   # (in, out, device) -> (bounds, kk, ksize) device int32 tensors
 
-Pullback = namedtuple('Pullback', 'data stack frames overlay color_mask')
+Pullback = namedtuple('Pullback', 'data stack frames overlay color_mask plaque', defaults=(None,))
 
 
 def _bicubic(x):
@@ -158,7 +158,7 @@ def normalize_volume(volume, swap_rb=True, device='cuda', return_minmax=False):
 
 
 def analyze_pullback(volume, models_dir, classes, output_size=(1000, 1000), names=None, render=False, swap_rb=True, close_iterations=1,
-                     clean=None, **segment_kwargs):
+                     clean=None, plaque=None, **segment_kwargs):
     """From a raw volume to the app's dict in one call: ``normalize_volume`` -> ``resize_pil_u8`` -> ``predict.segment_stack`` ->
     ``analysis.analyze_stack``; with ``render=True`` also ``postprocess.render_results``.  The frames go up once, at source size, and nothing
     comes back but the results.
@@ -169,12 +169,22 @@ def analyze_pullback(volume, models_dir, classes, output_size=(1000, 1000), name
     ``names`` default to ``'001', '002', ...`` (the ``slice+1:03d`` of convert_dicoms).  ``segment_kwargs`` go to ``segment_stack``
     (``batch_size``, ``compute_dtype``, ``use_graph``, ``device``).  ``clean``: None (default), True or a dict of ``cleanup.clean_stack``
     keywords: the mask stack is cleaned once (smoothing, keep-largest, hole fill) and the cleaned stack is measured, rendered and returned.
+    ``plaque``: None (default), True or a dict of ``polar.plaque_report`` keywords (``cap``, ``lipid``, ``thin_cap``, ``wide_arc``, ``ratio``):
+    the polar plaque report of the stack that is measured (after ``clean``), with the same names and, unless given, the same ``ratio``.
 
-    Returns ``Pullback(data, stack, frames, overlay, color_mask)``: the dict, the float32 mask stack and the uint8 RGB frames at output size
-    on the device; overlay and colour mask (uint8 CUDA [S,oh,ow,3]) with ``render=True``, else None."""
+    Returns ``Pullback(data, stack, frames, overlay, color_mask, plaque)``: the dict, the float32 mask stack and the uint8 RGB frames at
+    output size on the device; overlay and colour mask (uint8 CUDA [S,oh,ow,3]) with ``render=True``, else None; ``plaque`` the report or None."""
     from .analysis import analyze_stack
     from .postprocess import render_results
     from .predict import segment_stack
+    pk = None                                                                        # refused before any work is done
+    if plaque is not None and plaque is not False:
+        if plaque is not True and not isinstance(plaque, dict):
+            raise ValueError(f'plaque must be None, a bool or a dict of plaque_report keywords, got {plaque!r}')
+        pk = {} if plaque is True else dict(plaque)
+        bad = set(pk) - {'ratio', 'cap', 'lipid', 'thin_cap', 'wide_arc'}
+        if bad:
+            raise ValueError(f'unknown plaque_report keywords: {sorted(bad)}')
     frames = normalize_volume(volume, swap_rb=swap_rb, device=segment_kwargs.get('device', 'cuda'))
     S, H = int(frames.shape[0]), int(frames.shape[1])
     frames = resize_pil_u8(frames, (int(output_size[1]), int(output_size[0])))       # PIL sizes are (width, height)
@@ -189,4 +199,9 @@ def analyze_pullback(volume, models_dir, classes, output_size=(1000, 1000), name
     overlay = color_mask = None
     if render:
         overlay, color_mask = render_results(frames, stack, classes, close_iterations)
-    return Pullback(data, stack, frames, overlay, color_mask)
+    report = None
+    if pk is not None:
+        from .polar import plaque_report
+        pk.setdefault('ratio', int(H * 150 // 1000))
+        report = plaque_report(stack, names, **pk)
+    return Pullback(data, stack, frames, overlay, color_mask, report)
