@@ -484,6 +484,82 @@ int octseg_conv2d_backward_weight(int dtype, const void* x, const void* dy, floa
                                   int W, int Cin, int Cout, int R, int S, int stride, int pad,
                                   int transposed, void* stream);
 
+/* ---- single-op door to the NHWC sweep kernels (BatchNorm finalize / apply / backward, pools, resamplers, gates, gradient plumbing) ----
+ * One call = one launcher of csrc/kernels.h on `stream` (bn_bwd_finalize etc. included: the caller chains reduce -> finalize -> apply).
+ * ptrs: device pointers, in the order listed per op (NULL where an operand is optional), every one 16-byte aligned; iargs / fargs: the
+ * op's integer / float arguments in the order listed.  T = `dtype`; f = float32 whatever the dtype.  The counts must match the op.
+ * Refused before any launch: unknown op, wrong counts, a null required or misaligned pointer: OCTSEG_BAD_ARG; f16 on a training-only sweep
+ * (marked "train"): OCTSEG_BAD_DTYPE; an empty tensor, C not a multiple of the 16-byte vector (4 f32, 8 bf16 / f16), odd H or W for the
+ * 2x pools and the parity permute, k < 1, rows < 1: OCTSEG_BAD_SHAPE.  Buffer sizes are the caller's contract (oct_segmentation_amd/sweeps.py
+ * derives every one of them from the tensors' shapes). */
+typedef enum {
+  OCTSEG_SWEEP_BN_FINALIZE_TRAIN = 0,   /* ptrs slab f[rows][C][2], gamma, beta, running_mean, running_var, scale, shift, mean, rstd (f[C]),
+                                           part (double[32768]), counters (64 zeroed uint32); iargs rows, C; fargs count, momentum, eps */
+  OCTSEG_SWEEP_BN_FINALIZE_SMALL,       /* train. ptrs y T[count][C], gamma, beta, running_mean, running_var, scale, shift, mean, rstd; iargs count
+                                           (<= 1024), C; fargs momentum, eps */
+  OCTSEG_SWEEP_BN_FINALIZE_EVAL,        /* ptrs gamma, beta, running_mean, running_var, scale, shift; iargs C; fargs eps */
+  OCTSEG_SWEEP_BN_FINALIZE_FROZEN,      /* ptrs gamma, beta, running_mean, running_var, scale, shift, mean, rstd, coef f[C][2]; iargs C; fargs eps */
+  OCTSEG_SWEEP_BN_ACT,                  /* ptrs y, scale?, shift?, res?, rscale?, rshift?, post?, out, maskbits? (a byte per vector); iargs npix, C, relu */
+  /* the four BatchNorm-backward launchers share one pointer list: g, y, out?, maskbits?, scale, shift, mean, rstd, gamma, slab f[rows][C][2],
+   * dgamma, dbeta, coef f[C][2], dy, part (double[32768]), counters (64 zeroed uint32), res_grad?; iargs npix, C, mask (0 | 1 | 2), rows,
+   * res_store.  Each needs the operands its launcher reads or writes (SMALL: no slab / part / counters; REDUCE: g .. rstd and slab;
+   * FINALIZE: slab, dgamma, dbeta, coef, part, counters; APPLY: g .. gamma, coef, dy); dy may alias g. */
+  OCTSEG_SWEEP_BN_BWD_SMALL,            /* train; npix <= 1024 */
+  OCTSEG_SWEEP_BN_BWD_REDUCE,           /* train */
+  OCTSEG_SWEEP_BN_BWD_FINALIZE,
+  OCTSEG_SWEEP_BN_BWD_APPLY,            /* train */
+  OCTSEG_SWEEP_MASKED_ACCUM,            /* train. ptrs dst, g, out_mask?; iargs numel, store */
+  OCTSEG_SWEEP_POOL2X2_ACCUM,           /* train. ptrs dst T[N][H][W][C], src T[N][2H][2W][C]; iargs N, H, W, C, store */
+  OCTSEG_SWEEP_UP2_FILL,                /* ptrs in T[N][H][W][C], out T[N][2H][2W][C]; iargs N, H, W, C */
+  OCTSEG_SWEEP_RELU,                    /* ptrs in, mask?, out; iargs numel */
+  OCTSEG_SWEEP_ADD2,                    /* ptrs a, b, out; iargs numel */
+  OCTSEG_SWEEP_DROP_ELEM,               /* ptrs in, keep? f[numel], out; iargs numel; fargs mscale */
+  OCTSEG_SWEEP_MERGE_DROP,              /* ptrs a0, a1, a2, a3, m? f[N][C], out; iargs N, HW, C; fargs mscale */
+  OCTSEG_SWEEP_DROP_BWD,                /* ptrs gout, m? f[N][C], gin; iargs N, HW, C; fargs mscale */
+  OCTSEG_SWEEP_CHANNEL_SUM,             /* train. ptrs g T[npix][Cstride], out f[C] (accumulated); iargs npix, Cstride, C (any C >= 1) */
+  OCTSEG_SWEEP_TENSOR_STATS,            /* train. ptrs y T[npix][C], slab f[rows][C][2]; iargs npix, C, rows */
+  OCTSEG_SWEEP_MAXPOOL_FWD,             /* ptrs in T[N][H][W][C], out T[N][H/2][W/2][C], idx? (a byte per output element); iargs N, H, W, C */
+  OCTSEG_SWEEP_MAXPOOL_BWD_IDX,         /* train. ptrs idx, gout T[N][H/2][W/2][C], gin T[N][H][W][C]; iargs N, H, W, C, store */
+  OCTSEG_SWEEP_BILINEAR_RESIZE,         /* ptrs in T[N][IH][IW][C], out T[N][OH][OW][C]; iargs N, IH, IW, OH, OW, C */
+  OCTSEG_SWEEP_BILINEAR_RESIZE_ADJOINT, /* train. ptrs gout T[N][OH][OW][C], gin T[N][IH][IW][C]; iargs N, IH, IW, OH, OW, C */
+  OCTSEG_SWEEP_BILINEAR_ADJOINT,        /* train. ptrs gout T[N][H up][W up][C], gin T[N][H][W][C]; iargs N, H, W, C, up (>= 2) */
+  OCTSEG_SWEEP_BIN_MEAN,                /* ptrs in T[N][H][W][C], out T[N][k][k][C]; iargs N, H, W, C, k */
+  OCTSEG_SWEEP_BIN_MEAN_BWD,            /* train. ptrs gout T[N][k][k][C], gin T[N][H][W][C]; iargs N, H, W, C, k, accum */
+  OCTSEG_SWEEP_IMAGE_SUM,               /* ptrs in T[N][HW][C], out T[N][C]; iargs N, HW, C; fargs div */
+  OCTSEG_SWEEP_IMAGE_BCAST,             /* ptrs in T[N][C], out T[N][HW][C]; iargs N, HW, C, accum; fargs scale */
+  OCTSEG_SWEEP_SE_GATE,                 /* ptrs in T[N][HW][C], s T[N][C], out, s2? T[N][C]; iargs N, HW, C, accum */
+  OCTSEG_SWEEP_SE_DGATE,                /* train. ptrs g, x T[N][HW][C], s T[N][C], ds T[N][C], part f[N][shares(HW)][C], s2?, ds2?; iargs N, HW, C;
+                                           shares(HW) = clamp(HW / 64, 1, 64) */
+  OCTSEG_SWEEP_PARITY_PERMUTE,          /* ptrs src, dst (fine T[N][H][W][C] <-> coarse T[4N][H/2][W/2][C]); iargs N, H, W, C, to_coarse, accum */
+  OCTSEG_SWEEP_MOSAIC,                  /* ptrs src, dst (fine T[N][H][W][C] <-> mosaic T[N][r (hs + 1) + 1][r (ws + 1) + 1][C], hs = ceil(H / r));
+                                           iargs N, H, W, C, r, to_mosaic, accum */
+  OCTSEG_SWEEP_DW_CONV,                 /* depthwise 3x3, dilation = padding = dil, on channel slices.  ptrs in T[N][H][W][inC], out T[N][H][W][outC],
+                                           w f[9][wC]; iargs inC, ic0, outC, oc0, wC, wc0, N, H, W, C, dil, flip, accum (wC, wc0 multiples of 4) */
+  OCTSEG_SWEEP_DW_WGRAD,                /* train. ptrs in T[N][H][W][inC], gout T[N][H][W][goC], dw f[9][wC] (accumulated); iargs inC, ic0, goC, oc0,
+                                           wC, wc0, N, H, W, C, dil */
+  OCTSEG_SWEEP_CAM_SEED,                /* train. ptrs seed f[B][C][HW], dlogits T[B][HW][CP] (zeros beyond C); iargs B, C, HW, CP (8 | 16) */
+  /* depthwise K x K (3 | 5), stride 1 | 2, top / left padding `pad` (TF static "same"); w / dw: f[K][K][C] */
+  OCTSEG_SWEEP_DWG_FWD,                 /* ptrs in T[N][H][W][C], out T[N][OH][OW][C], w; iargs N, H, W, C, OH, OW, K, stride, pad */
+  OCTSEG_SWEEP_DWG_BWD_DATA,            /* train. ptrs gout T[N][OH][OW][C], gin T[N][H][W][C], w; iargs as DWG_FWD, accum */
+  OCTSEG_SWEEP_DWG_BWD_W,               /* train. ptrs in, gout, dw (accumulated); iargs as DWG_FWD */
+  OCTSEG_SWEEP_BNX_FWD,                 /* out = act(y scale + shift) dscale[n] + post.  ptrs y, scale?, shift?, dscale? f[npix / hw], post?, out;
+                                           iargs npix, hw (pixels per image), C, act (0 identity | 1 swish) */
+  OCTSEG_SWEEP_BNX_BWD,                 /* train. out = g dscale[n] act'(y scale + shift).  ptrs y?, scale?, shift?, dscale?, g, out; iargs as BNX_FWD */
+  OCTSEG_SWEEP_DICE_BWD,                /* train. ptrs logits, target f[B][C][HW], sums double[1 + B][C][4] (I, S, T, BCE totals first), dlogits T[B][HW][CP]
+                                           (zeros beyond C); iargs B, C, HW, CP (8 | 16), loss kind (0 dice | 1 bce | 2 both); fargs grad_scale */
+  /* GroupNorm(G) + ReLU (+ bilinear x2, align_corners) of [N][HW][C]; C <= 1024 with C / vector a divisor of 256; S = clamp(HW / 1024, 1, 64) */
+  OCTSEG_SWEEP_GN_FORWARD,              /* ptrs y, gamma, beta, out T[N][H up][W up][C], part f[N][S][C][2], ss f[N][C][2], stat f[N][G][2]; iargs N, H, W,
+                                           C, G, up (1 | 2); fargs eps */
+  OCTSEG_SWEEP_GN_BACKWARD,             /* train. ptrs y, g, dy (may alias g), gamma, dgamma, dbeta (accumulated), part, ss, stat (the forward's),
+                                           coef f[N][G][2]; iargs N, HW, C, G */
+  /* squeeze-excite excitation s = W2 act(W1 m + b1) + b2 on pooled vectors; W1 f[R][C], W2 f[C][R]; h, dh f[N][R] */
+  OCTSEG_SWEEP_SEFC_FWD,                /* ptrs m T[N][C], s T[N][C], w1, b1, w2, b2, h; iargs N, C, R, act (0 ReLU | 1 swish) */
+  OCTSEG_SWEEP_SEFC_BWD,                /* train. ptrs m, ds, dm T[N][C], w1, w2, h, dh, dw1?, db1?, dw2?, db2? (accumulated; all four or none); iargs as SEFC_FWD */
+  OCTSEG_SWEEP_NUM_OPS
+} octseg_sweep;
+int octseg_sweep_op(int op, int dtype, const void* const* ptrs, int nptrs, const long long* iargs, int niargs, const double* fargs,
+                    int nfargs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

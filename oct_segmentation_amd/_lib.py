@@ -121,6 +121,8 @@ SYMBOLS = {
     'octseg_conv2d_forward': (C.c_int, [C.c_int, _P, _P, _P, _P] + [C.c_int] * 10 + [_P, _P]),
     'octseg_conv2d_backward_data': (C.c_int, [C.c_int, _P, _P, _P] + [C.c_int] * 10 + [_P, _P]),
     'octseg_conv2d_backward_weight': (C.c_int, [C.c_int, _P, _P, _P] + [C.c_int] * 10 + [_P]),
+    # one launcher of the NHWC sweep kernels per call (csrc/sweep_api.cpp; wrappers in sweeps.py)
+    'octseg_sweep_op': (C.c_int, [C.c_int, C.c_int, C.POINTER(_P), C.c_int, C.POINTER(C.c_longlong), C.c_int, C.POINTER(C.c_double), C.c_int, _P]),
 }
 
 _lib = None

@@ -429,20 +429,25 @@ __global__ __launch_bounds__(256) void bilinear_resize_adjoint_kernel(const void
     stv<T>(gin, bidx * vpc + v0 + cv, EV<T>::pack(acc));
   }
 }
+bool bilinear_adjoint_grid(long long npx, int& gy, int& gz) {
+  gy = (int)npx; gz = 1;
+  if (npx < 1) return false;
+  if (npx > 65535) {                       // one workgroup per source pixel: factor the count into grid.y x grid.z exactly
+    gy = 0;
+    for (int d = 65535; d >= 1; --d) if (npx % d == 0) { gy = d; break; }
+    if (npx / gy > 65535) return false;
+    gz = (int)(npx / gy);
+  }
+  return true;
+}
 hipError_t launch_bilinear_resize_adjoint(int dtype, const void* gout, void* gin, int N, int IH, int IW, int OH, int OW, int C, hipStream_t st) {
   OCTSEG_NO_F16(dtype);
   const int vec = ev_vec(dtype);
   if (C % vec != 0) return hipErrorInvalidValue;
   const int vpc = C / vec;
   const float sy = lerp_scale(IH, OH), sx = lerp_scale(IW, OW);
-  const long long npx = (long long)N * IH * IW;
-  int gy = (int)npx, gz = 1;
-  if (npx > 65535) {                       // one workgroup per source pixel: factor the count into grid.y x grid.z exactly
-    gy = 0;
-    for (int d = 65535; d >= 1; --d) if (npx % d == 0) { gy = d; break; }
-    gz = (int)(npx / gy);
-    if (gz > 65535) return hipErrorInvalidValue;
-  }
+  int gy, gz;
+  if (!bilinear_adjoint_grid((long long)N * IH * IW, gy, gz)) return hipErrorInvalidValue;
   const dim3 grid((vpc + DW_CH - 1) / DW_CH, gy, gz);
   OCTSEG_LAUNCH_TRAIN(bilinear_resize_adjoint_kernel, grid, dim3(256), gout, gin, IH, IW, OH, OW, vpc, sy, sx);
   return hipGetLastError();

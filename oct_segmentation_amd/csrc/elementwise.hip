@@ -333,18 +333,24 @@ template <typename T>
 __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const BnBwdArgs a) {
   constexpr int VEC = EV<T>::VEC;
   __shared__ float red[256][VEC * 2 + 1];
-  const int vpc = a.C / VEC;                     // vectors per pixel (power of two)
+  const int vpc = a.C / VEC;                     // vectors per pixel (any count: below 256 the threads past tpv * vpc idle, from 256 on
+                                                 // grid.y walks chunks of 256 vectors and the last chunk may be partly empty)
   const int tpv = vpc >= 256 ? 1 : 256 / vpc;    // threads sharing one channel vector
   const int cv = (vpc >= 256 ? blockIdx.y * 256 : 0) + (threadIdx.x % (vpc >= 256 ? 256 : vpc));
   const int pl = vpc >= 256 ? 0 : threadIdx.x / vpc;
+  const bool live = cv < vpc && pl < tpv;        // (no early return: the barrier below stays block-uniform)
   const int c = cv * VEC;
   float sc[VEC], sh[VEC], mu[VEC], rs[VEC];
 #pragma unroll
-  for (int i = 0; i < VEC; ++i) { sc[i] = a.scale[c + i]; sh[i] = a.shift[c + i]; mu[i] = a.mean[c + i]; rs[i] = a.rstd[c + i]; }
+  for (int i = 0; i < VEC; ++i) { sc[i] = 0.f; sh[i] = 0.f; mu[i] = 0.f; rs[i] = 0.f; }
+  if (live) {
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) { sc[i] = a.scale[c + i]; sh[i] = a.shift[c + i]; mu[i] = a.mean[c + i]; rs[i] = a.rstd[c + i]; }
+  }
   float s1[VEC], s2[VEC];
 #pragma unroll
   for (int i = 0; i < VEC; ++i) { s1[i] = 0.f; s2[i] = 0.f; }
-  for (size_t p = (size_t)blockIdx.x * tpv + pl; p < a.npix; p += (size_t)gridDim.x * tpv) {
+  for (size_t p = (size_t)blockIdx.x * tpv + pl; live && p < a.npix; p += (size_t)gridDim.x * tpv) {
     const size_t v = p * vpc + cv;
     float g[VEC], y[VEC];
     EV<T>::unpack(ldv<T>(a.g, v), g);
@@ -370,7 +376,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const BnBwdArgs a) {
 #pragma unroll
   for (int i = 0; i < VEC; ++i) { red[threadIdx.x][i] = s1[i]; red[threadIdx.x][VEC + i] = s2[i]; }
   __syncthreads();
-  if (pl == 0) {
+  if (live && pl == 0) {
     for (int k = 1; k < tpv; ++k)
 #pragma unroll
       for (int i = 0; i < VEC; ++i) { s1[i] += red[threadIdx.x + k * vpc][i]; s2[i] += red[threadIdx.x + k * vpc][VEC + i]; }
@@ -383,7 +389,7 @@ hipError_t launch_bn_bwd_reduce(int dtype, const BnBwdArgs& a, hipStream_t st) {
   OCTSEG_NO_F16(dtype);
   const int VEC = ev_vec(dtype);
   const int vpc = a.C / VEC;
-  dim3 grid(a.rows, vpc >= 256 ? vpc / 256 : 1);
+  dim3 grid(a.rows, vpc >= 256 ? (vpc + 255) / 256 : 1);   // (RegNetY-120 stage 4: 2240 channels = 280 bf16 vectors, two chunks)
   OCTSEG_LAUNCH_TRAIN(bn_bwd_reduce_kernel, grid, dim3(256), a);
   return hipGetLastError();
 }

@@ -223,8 +223,9 @@ __global__ __launch_bounds__(256) void bilinear_adjoint_kernel(const void* gout,
     const int iy = (int)(p % H);
     const int n = (int)(p / H);
     // candidate outputs: those whose source coordinate lies in (i - 1, i + 1); two guard outputs on either side absorb the float rounding
-    const int oy0 = max(0, (int)((float)(iy - 1) * inv_sy) - 1), oy1 = min(OH - 1, (int)((float)(iy + 1) * inv_sy) + 2);
-    const int ox0 = max(0, (int)((float)(ix - 1) * inv_sx) - 1), ox1 = min(OW - 1, (int)((float)(ix + 1) * inv_sx) + 2);
+    // (a one-pixel axis has scale 0 and no inverse: every output reads that pixel)
+    const int oy0 = max(0, (int)((float)(iy - 1) * inv_sy) - 1), oy1 = sy > 0.f ? min(OH - 1, (int)((float)(iy + 1) * inv_sy) + 2) : OH - 1;
+    const int ox0 = max(0, (int)((float)(ix - 1) * inv_sx) - 1), ox1 = sx > 0.f ? min(OW - 1, (int)((float)(ix + 1) * inv_sx) + 2) : OW - 1;
     float acc[VEC];
 #pragma unroll
     for (int i = 0; i < VEC; ++i) acc[i] = 0.f;

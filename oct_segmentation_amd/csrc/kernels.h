@@ -290,6 +290,7 @@ hipError_t launch_bin_mean(int dtype, const void* in, void* out, int N, int H, i
 hipError_t launch_bin_mean_bwd(int dtype, const void* gout, void* gin, int N, int H, int W, int C, int k, int accum, hipStream_t st);
 hipError_t launch_bilinear_resize(int dtype, const void* in, void* out, int N, int IH, int IW, int OH, int OW, int C, hipStream_t st);          // align_corners=True, any sizes
 hipError_t launch_bilinear_resize_adjoint(int dtype, const void* gout, void* gin, int N, int IH, int IW, int OH, int OW, int C, hipStream_t st);
+bool bilinear_adjoint_grid(long long npx, int& gy, int& gz);   // its one-workgroup-per-source-pixel grid, grid.y x grid.z = npx exactly; false: no such pair
 hipError_t launch_relu(int dtype, const void* in, const void* mask, void* out, size_t numel, hipStream_t st);                                   // mask == nullptr: max(in, 0); else in where mask > 0
 
 // serving: out[n][y][x][out_ch] = (logits[n][ch] nearest-resized to OH x OW) > 0, out has OC channels per pixel
