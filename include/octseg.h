@@ -484,6 +484,56 @@ int octseg_conv2d_backward_weight(int dtype, const void* x, const void* dy, floa
                                   int W, int Cin, int Cout, int R, int S, int stride, int pad,
                                   int transposed, void* stream);
 
+/* ---- single-layer door to the conv kernels' fused operand and epilogue paths (csrc/conv_api.cpp; wrappers in convops.py) ----
+ * One call = the launches of ONE conv layer pass, with the descriptors the plan builds for it: the lazy BatchNorm affine + ReLU of every
+ * source, nearest-x2 reads, channel concatenation, the eval fold (wscale, bias, relu_out), the BatchNorm statistics slab, several
+ * data-gradient destinations with accum / pool, the head's NCHW f32 store.  The routing is launch_conv's / launch_wgrad's own.
+ *   geometry   N, virtual input H x W (after `up`), R in {1, 3} (4 with transposed = ConvTranspose2d k4 s2 p1), stride 1 | 2, pad <= R / 2;
+ *              OH x OW = (H + 2 pad - R) / stride + 1 (transposed: 2H x 2W)
+ *   sources    nsrc <= 5 tensors T[N][H >> up][W >> up][C], concatenated in order (sum of C = Cin); scale / shift f[C] (both or neither):
+ *              relu?(x * scale + shift) rounded to T on load, padding stays 0; relu only with the affine
+ *   w          f[R][R][Cout][Cin] (arena layout); forward and data gradient pack it into `scratch` (>= octseg_conv2d_scratch_bytes())
+ *   forward    wscale f[Cout] (folded into the packed image as launch_pack_all folds it for eval), bias f[Cout], relu_out (needs bias, excludes
+ *              stat_slab); stat_slab f[slab_row0 + rows][Cout][2] = per row (sum y, sum y^2) of the f32 y (bias included) before the storage
+ *              rounding, rows = octseg_conv_layer_slab_rows(); dst[0] = T[N][OH][OW][Cout] (+ accum), or head = 1: f32 NCHW [N][Cout][OH][OW]
+ *   data grad  dy T[N][OH][OW][Cout]; dst[i] = gradient of source i: T[N][H][W][C_i] (+ accum), or pool = 1 (an `up` source at stride 1):
+ *              T[N][H / 2][W / 2][C_i], every 2x2 quad summed in the epilogue.  A stride-2 1x1 layer covers one pixel parity only: accum = 1
+ *              over a zeroed tensor, as the plan does it
+ *   weight grad  the same sources (affine included), dy, and dW f[R][R][Cout][Cin] ACCUMULATED with atomics onto what is there
+ * Refused before any launch: a null required or misaligned (16 B) pointer, scale without shift, relu without the affine, pool elsewhere than
+ * stated, relu_out with stat_slab or without bias, bias with stat_slab where the launch would go to gemm1x1 (the plan never builds it),
+ * a slab / accum / transposed layer in head mode, forward-only fields in a gradient mode, a scratch too small: OCTSEG_BAD_ARG; more than 5
+ * sources, extents that do not match H >> up, C / Cout not whole 16-byte vectors (4 f32, 8 bf16 / f16; a head's Cout is free), unsupported
+ * geometry: OCTSEG_BAD_SHAPE; f16 in a gradient mode: OCTSEG_BAD_DTYPE. */
+#define OCTSEG_CONV_MAX_SRC 5
+typedef enum { OCTSEG_CONV_FORWARD = 0, OCTSEG_CONV_BACKWARD_DATA = 1, OCTSEG_CONV_BACKWARD_WEIGHT = 2 } octseg_conv_mode;
+/* octseg_conv_layer_route: forward / data gradient launches ...; -1 = a launch without taps (nothing runs) */
+typedef enum { OCTSEG_ROUTE_THIN = 0, OCTSEG_ROUTE_GEMM1X1, OCTSEG_ROUTE_CONV3X3P, OCTSEG_ROUTE_MFMA16, OCTSEG_ROUTE_MFMA11,
+               OCTSEG_ROUTE_MFMA_WIDEN } octseg_conv_route;
+/* ... weight gradient launches (CONVT16: the four parities of a ConvTranspose2d in one launch) */
+typedef enum { OCTSEG_WROUTE_THIN = 0, OCTSEG_WROUTE_WGRAD1X1, OCTSEG_WROUTE_CONVT16, OCTSEG_WROUTE_MFMA } octseg_wgrad_route;
+typedef struct {
+  const void* ptr; const float* scale; const float* shift;
+  int C, H, W, up, relu;          /* H, W: stored extents */
+} octseg_conv_src;
+typedef struct { void* ptr; int accum, pool; } octseg_conv_dst;
+typedef struct {
+  int N, H, W, Cin, Cout, R, stride, pad, transposed;
+  int nsrc;
+  octseg_conv_src src[OCTSEG_CONV_MAX_SRC];
+  const float* w; const float* wscale; const float* bias;
+  int relu_out;
+  float* stat_slab; int slab_row0;
+  int head;
+  octseg_conv_dst dst[OCTSEG_CONV_MAX_SRC];
+  const void* dy; float* dW;
+  void* scratch; size_t scratch_bytes;
+} octseg_conv_layer_desc;
+int octseg_conv_layer_op(int mode, int dtype, const octseg_conv_layer_desc* desc, void* stream);
+/* which kernel each launch of that call runs (route_per_launch: at least 4 ints), and the slab rows of a forward; nothing is launched */
+int octseg_conv_layer_route(int mode, int dtype, const octseg_conv_layer_desc* desc, int* route_per_launch, int* nlaunch);
+int octseg_conv_layer_slab_rows(int dtype, const octseg_conv_layer_desc* desc, int* rows);
+
 /* ---- single-op door to the NHWC sweep kernels (BatchNorm finalize / apply / backward, pools, resamplers, gates, gradient plumbing) ----
  * One call = one launcher of csrc/kernels.h on `stream` (bn_bwd_finalize etc. included: the caller chains reduce -> finalize -> apply).
  * ptrs: device pointers, in the order listed per op (NULL where an operand is optional), every one 16-byte aligned; iargs / fargs: the

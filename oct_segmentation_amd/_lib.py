@@ -47,6 +47,26 @@ class BNInfo(C.Structure):
     _fields_ = [('name', C.c_char * 128), ('C', C.c_int), ('mean_offset', C.c_size_t), ('var_offset', C.c_size_t)]
 
 
+class ConvSrc(C.Structure):
+    _fields_ = [('ptr', C.c_void_p), ('scale', C.c_void_p), ('shift', C.c_void_p), ('C', C.c_int), ('H', C.c_int), ('W', C.c_int),
+                ('up', C.c_int), ('relu', C.c_int)]
+
+
+class ConvDst(C.Structure):
+    _fields_ = [('ptr', C.c_void_p), ('accum', C.c_int), ('pool', C.c_int)]
+
+
+CONV_MAX_SRC = 5
+
+
+class ConvLayerDesc(C.Structure):   # octseg_conv_layer_desc
+    _fields_ = [('N', C.c_int), ('H', C.c_int), ('W', C.c_int), ('Cin', C.c_int), ('Cout', C.c_int), ('R', C.c_int), ('stride', C.c_int),
+                ('pad', C.c_int), ('transposed', C.c_int), ('nsrc', C.c_int), ('src', ConvSrc * CONV_MAX_SRC), ('w', C.c_void_p),
+                ('wscale', C.c_void_p), ('bias', C.c_void_p), ('relu_out', C.c_int), ('stat_slab', C.c_void_p), ('slab_row0', C.c_int),
+                ('head', C.c_int), ('dst', ConvDst * CONV_MAX_SRC), ('dy', C.c_void_p), ('dW', C.c_void_p), ('scratch', C.c_void_p),
+                ('scratch_bytes', C.c_size_t)]
+
+
 # every exported symbol with (restype, argtypes), in the order of include/octseg.h; tests check the library exports all of them
 _P = C.c_void_p
 LOSS_KINDS = {'dice': 0, 'bce': 1, 'dice+bce': 2}
@@ -121,6 +141,10 @@ SYMBOLS = {
     'octseg_conv2d_forward': (C.c_int, [C.c_int, _P, _P, _P, _P] + [C.c_int] * 10 + [_P, _P]),
     'octseg_conv2d_backward_data': (C.c_int, [C.c_int, _P, _P, _P] + [C.c_int] * 10 + [_P, _P]),
     'octseg_conv2d_backward_weight': (C.c_int, [C.c_int, _P, _P, _P] + [C.c_int] * 10 + [_P]),
+    # one conv layer pass with the plan's fused descriptors per call, and its routing queries (csrc/conv_api.cpp; wrappers in convops.py)
+    'octseg_conv_layer_op': (C.c_int, [C.c_int, C.c_int, C.POINTER(ConvLayerDesc), _P]),
+    'octseg_conv_layer_route': (C.c_int, [C.c_int, C.c_int, C.POINTER(ConvLayerDesc), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    'octseg_conv_layer_slab_rows': (C.c_int, [C.c_int, C.POINTER(ConvLayerDesc), C.POINTER(C.c_int)]),
     # one launcher of the NHWC sweep kernels per call (csrc/sweep_api.cpp; wrappers in sweeps.py)
     'octseg_sweep_op': (C.c_int, [C.c_int, C.c_int, C.POINTER(_P), C.c_int, C.POINTER(C.c_longlong), C.c_int, C.POINTER(C.c_double), C.c_int, _P]),
 }

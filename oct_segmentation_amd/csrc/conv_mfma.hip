@@ -1669,13 +1669,20 @@ static bool flatten_1x1(ConvArgs& a) {
 
 // Which kernel runs a conv launch: decided HERE, once, for launch_conv and for conv_num_mtiles_flat (the BatchNorm statistics slab that the chosen
 // kernel writes has one row per M tile / workgroup of THAT kernel).  A launch with per-source tap subsets belongs to conv_mfma's masked loop.
-enum ConvRoute { ROUTE_THIN, ROUTE_GEMM1X1, ROUTE_CONV3X3P, ROUTE_MFMA };
-static ConvRoute conv_route(const ConvArgs& a, int dtype) {
+ConvRoute conv_route(const ConvArgs& a, int dtype) {
   if (a.taps_per_src > 0) return ROUTE_MFMA;
   if (thin_conv_eligible(a, dtype)) return ROUTE_THIN;
   if (gemm1x1_eligible(a, dtype)) return ROUTE_GEMM1X1;
   if (conv3x3p_eligible(a, dtype)) return ROUTE_CONV3X3P;
   return ROUTE_MFMA;
+}
+
+// ... and, for a launch that conv_route leaves to conv_mfma_kernel, the tiling it runs with (launch_conv's flattening applied)
+int conv_mfma_tile(const ConvArgs& a0, int dtype) {
+  ConvArgs a = a0;
+  if (a.taps_per_src == 0) flatten_1x1(a);
+  const Choice c = choose(a, (int)dtype_size(dtype));
+  return c.tile11 == 1 ? TILE_11 : c.v.NT == 4 ? TILE_WIDE_N : TILE_16;
 }
 
 int conv_num_mtiles_flat(const ConvArgs& a0, int dtype) {

@@ -1016,7 +1016,7 @@ hipError_t launch_dice_bwd(int dtype, const DiceArgs& a, float grad_scale, void*
 // XOR is applied when the MFMA B fragments are read, so the slab can be DMA-copied linearly).
 template <typename T>
 __global__ __launch_bounds__(256) void pack_image_kernel(const float* w, void* img, int taps, int O, int I, int transpose,
-                                                         int BN, int RB, int nchunks, int ntiles) {
+                                                         int BN, int RB, int nchunks, int ntiles, const float* oscale) {
   constexpr int VEC = EV<T>::VEC;
   const int VPR = RB / 16, KC = RB / (int)sizeof(T), swz_div = 256 / RB;
   const int rows = transpose ? I : O, K = transpose ? O : I;
@@ -1036,21 +1036,22 @@ __global__ __launch_bounds__(256) void pack_image_kernel(const float* w, void* i
       const int c = c0 + i;
       float val = 0.f;
       if (co < rows && c < K) val = transpose ? w[((size_t)tap * O + c) * I + co] : w[((size_t)tap * O + co) * I + c];
+      if (oscale != nullptr && !transpose && co < rows) val *= oscale[co];   // (pack_all_kernel's eval fold)
       x[i] = val;
     }
     stv<T>(img, v, EV<T>::pack(x));
   }
 }
 hipError_t launch_pack_weight_image(int dtype, const float* w, void* img, int taps, int O, int I, int transpose,
-                                    const ConvPackInfo& p, hipStream_t st) {
+                                    const ConvPackInfo& p, hipStream_t st, const float* oscale) {
   const size_t total = (size_t)taps * p.nchunks * p.ntiles * p.BN * (p.RB / 16);
   const int gr = grid_for(total, 256, 4096);
   if (dtype == DT_F16)
-    hipLaunchKernelGGL(pack_image_kernel<f16_t>, dim3(gr), dim3(256), 0, st, w, img, taps, O, I, transpose, p.BN, p.RB, p.nchunks, p.ntiles);
+    hipLaunchKernelGGL(pack_image_kernel<f16_t>, dim3(gr), dim3(256), 0, st, w, img, taps, O, I, transpose, p.BN, p.RB, p.nchunks, p.ntiles, oscale);
   else if (dtype == DT_F32)
-    hipLaunchKernelGGL(pack_image_kernel<float>, dim3(gr), dim3(256), 0, st, w, img, taps, O, I, transpose, p.BN, p.RB, p.nchunks, p.ntiles);
+    hipLaunchKernelGGL(pack_image_kernel<float>, dim3(gr), dim3(256), 0, st, w, img, taps, O, I, transpose, p.BN, p.RB, p.nchunks, p.ntiles, oscale);
   else
-    hipLaunchKernelGGL(pack_image_kernel<bf16_t>, dim3(gr), dim3(256), 0, st, w, img, taps, O, I, transpose, p.BN, p.RB, p.nchunks, p.ntiles);
+    hipLaunchKernelGGL(pack_image_kernel<bf16_t>, dim3(gr), dim3(256), 0, st, w, img, taps, O, I, transpose, p.BN, p.RB, p.nchunks, p.ntiles, oscale);
   return hipGetLastError();
 }
 

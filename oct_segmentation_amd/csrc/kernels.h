@@ -15,6 +15,19 @@ static inline size_t conv_image_bytes(const ConvPackInfo& p, int wtaps) {
   return (size_t)wtaps * p.nchunks * p.ntiles * p.BN * p.RB;
 }
 hipError_t launch_conv(int dtype, const ConvArgs& a, hipStream_t st);
+// Which kernel launch_conv gives a launch to (thin.hip, gemm1x1.hip, conv3x3p.hip or conv_mfma_kernel), and conv_mfma_kernel's tiling of a
+// ROUTE_MFMA launch: 16-pixel-wide tiles (16 or 8 rows), 11 x 11 tiles, or the 256-channel wide-N tile.  Queries: nothing is launched.
+enum ConvRoute { ROUTE_THIN, ROUTE_GEMM1X1, ROUTE_CONV3X3P, ROUTE_MFMA };
+enum ConvTile { TILE_16, TILE_11, TILE_WIDE_N };
+ConvRoute conv_route(const ConvArgs& a, int dtype);
+int conv_mfma_tile(const ConvArgs& a, int dtype);
+// How a destination element is rounded (T = the storage type; `y` = the f32 accumulator + bias, after relu_out):
+//   conv_mfma_kernel, gemm1x1, conv3x3p (the tile is transposed through LDS as T):
+//     store  T(y);   accum  T(f32(T(y)) + old);   pool  T(old + T(y00) + T(y01) + T(y10) + T(y11)), the sum in f32 in that order
+//     -- bit for bit what a T temp followed by masked_accum / pool2x2_accum gives;
+//   thin.hip (the accumulators go to memory straight from registers):
+//     store  T(y);   accum  T(y + old);           pool  T(old + (y00 + y10 + y01 + y11)), nothing rounded before the last step.
+// BatchNorm statistics are always those of the f32 `y`, over the pixels inside the map.  tests/conv_ref.py states both rules.
 bool conv_masked_eligible(const ConvArgs& a, int dtype);   // launches with per-source tap subsets (ConvArgs::taps_per_src): can the masked loop take this one?
 
 // gemm1x1.hip: stride-1, single-source 1x1 convs and their data gradients as a persistent GEMM (2-byte dtypes); consumes the same
@@ -124,6 +137,8 @@ hipError_t launch_se_dgate(int dtype, const void* g, const void* x, const void* 
 
 // wgrad_mfma.hip
 hipError_t launch_wgrad(int dtype, const WgradArgs& a, hipStream_t st);
+enum WgradRoute { WROUTE_THIN, WROUTE_1X1, WROUTE_MFMA };
+WgradRoute wgrad_route(const WgradArgs& a, int dtype);   // the kernel launch_wgrad gives a launch to (a query: nothing is launched)
 // wgrad1x1.hip: stride-1 1x1 weight gradients (bf16, 64-divisible channel counts, flattened pixel list) as an LDS-DMA ring pipeline;
 // wgrad_convt.hip: ConvTranspose2d(k4, s2, p1) weight gradient, all four output parities (16 taps) in one launch; `a` = any of the four
 // per-parity launches of the transposed form (they share sources, extents, dy and dW)
@@ -231,8 +246,9 @@ hipError_t launch_dice_bwd(int dtype, const DiceArgs& a, float grad_scale, void*
 // weight packing: master fp32 [taps][O][I] -> LDS-image slabs of a conv launch.  transpose = 0: rows are
 // O, K runs over I (forward);  transpose = 1: rows are I, K runs over O (data gradient); K is padded
 // to Kpad (>= the contraction length the launch uses).
+// oscale (forward images only, nullable): W'[o][i] = W[o][i] * oscale[o] in f32 before the rounding to T -- launch_pack_all's eval fold.
 hipError_t launch_pack_weight_image(int dtype, const float* w, void* img, int taps, int O, int I, int transpose,
-                                    const ConvPackInfo& p, hipStream_t st);
+                                    const ConvPackInfo& p, hipStream_t st, const float* oscale = nullptr);
 
 // every weight image of a plan in one launch (job table + prefix sums live in the workspace)
 struct PackJob { size_t src_off /*floats*/, dst_off /*bytes*/; int taps, O, I, transpose, BN, RB, nchunks, ntiles;

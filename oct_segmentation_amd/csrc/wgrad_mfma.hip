@@ -543,14 +543,23 @@ static void flatten_1x1(WgradArgs& a) {
   for (int i = 0; i < a.nsrc; ++i) { a.src[i].H = rows; a.src[i].W = TW; }
 }
 
+// Which kernel runs a weight-gradient launch: decided here, once, for launch_wgrad and for the single-layer entry's route query.
+WgradRoute wgrad_route(const WgradArgs& a0, int dtype) {
+  if (thin_wgrad_eligible(a0, dtype)) return WROUTE_THIN;
+  WgradArgs a = a0;
+  flatten_1x1(a);
+  return wgrad1x1_eligible(a, dtype) ? WROUTE_1X1 : WROUTE_MFMA;
+}
+
 hipError_t launch_wgrad(int dtype, const WgradArgs& a0, hipStream_t st) {
   if (dtype == DT_F16) return hipErrorInvalidValue;   // f16 is an eval-forward dtype
 
   if (a0.ntaps <= 0) return hipSuccess;
-  if (thin_wgrad_eligible(a0, dtype)) return launch_thin_wgrad(dtype, a0, st);
+  const WgradRoute route = wgrad_route(a0, dtype);
+  if (route == WROUTE_THIN) return launch_thin_wgrad(dtype, a0, st);
   WgradArgs a = a0;
   flatten_1x1(a);
-  if (wgrad1x1_eligible(a, dtype)) return launch_wgrad1x1(dtype, a, st);
+  if (route == WROUTE_1X1) return launch_wgrad1x1(dtype, a, st);
   if (a.ntaps == 1 || a.ntaps == 4 || a.ntaps == 9) {
     if (dtype == DT_F32) {
       if (a.ntaps == 1) return launch_wgrad_t<float, 1>(a, dtype, st);

@@ -3,7 +3,8 @@
 Each case runs forward, data gradient and weight gradient through the C ABI
 single-op entry points and compares with torch.nn.functional on the CPU.
 Tolerances: fp32 path 1e-4 relative to the output scale (BASELINE north_star);
-bf16 path 2e-2 (bf16 inputs, f32 accumulate).
+bf16 path 2e-2 (bf16 inputs, f32 accumulate).  The fused operand and epilogue paths (lazy affine, up, concat, slab, fold, accum / pool,
+head) are pinned exactly, route by route, in tests/test_gpu_convops.py; the large shapes here keep the default routing.
 """
 import pytest
 import torch
