@@ -43,6 +43,9 @@
  *   octseg_stack_components / octseg_stack_cleanup / octseg_components_scratch_bytes
  *                                      MaskProcessor.smooth_mask / .remove_artifacts, which process_pair runs over every annotated object
  *                                      (src/data/mask_processor.py:5-37, src/data/convert_int_to_cv.py:191-199)
+ *   octseg_stack_boundary / octseg_stack_distance / octseg_pair_distance_counts / _keys / _min / octseg_distance_scratch_bytes
+ *                                      (no reference counterpart) exact squared Euclidean distance maps of the mask planes, the directed
+ *                                      boundary-distance lists behind HD / HD95 / ASSD, the smallest distance between two classes
  *   octseg_volume_normalize            cv2.normalize(slice, None, 0, 255, NORM_MINMAX, CV_8U) + cvtColor(BGR2RGB) of every slice of a DICOM's
  *                                      pixel_array (src/data/convert_dicoms.py:71-81, src/app/tools/analysis.py:167-177)
  *   octseg_resize_pil_u8               data_processing's Image.open(p).resize(output_size), Pillow's default BICUBIC (src/data/utils.py:187)
@@ -345,6 +348,46 @@ int octseg_stack_components(const float* stack, int N, int H, int W, int channel
                             int* top, void* stream);
 int octseg_stack_cleanup(const float* stack, int N, int H, int W, int channels, int smooth_k, int keep, int min_area, int fill_holes, void* scratch,
                          size_t scratch_bytes, float* out, int* ncomp, int* top, void* stream);
+
+/* Boundary distances (no reference counterpart: the reference scores overlap only; what is restated here are the definitions of DESIGN.md
+ * section 5i, pinned to scipy.ndimage by tests/distance_ref.py).  stack / src / dst: device f32 [N][H][W][channels], any value != 0 is set; a plane
+ * is one (slice, channel) pair.  A PART of a plane is 0 the set pixels, 1 the clear pixels inside the frame, or 2 the boundary
+ *   b = m & ~erode(m) with the 4-neighbour cross, the outside of the frame counting as clear, so that a set pixel on the frame edge is boundary
+ *   (scipy: m & ~binary_erosion(m, generate_binary_structure(2, 1), border_value=0)).
+ * The squared distance of pixel (y, x) to a target part T is d2 = min over (y', x') in T of (y - y')^2 + (x - x')^2, pixel centre to pixel centre,
+ * exact in int32 (scipy: rint(distance_transform_edt(~T)^2)); 0 on T itself; OCTSEG_DIST_NONE when T is empty.  Integer arithmetic only: results
+ * EQUAL the restatement's, no tolerance.
+ * scratch: device, 8-byte aligned, scratch_bytes >= octseg_distance_scratch_bytes(N, H, W, channels_a, channels_b, pairs) (one-stack calls:
+ * channels_a = channels, channels_b = 0, pairs = 0; 0 is returned for extents the calls refuse).
+ *
+ * octseg_stack_boundary: out f32 [N][H][W][channels] (0.0 / 1.0, must not alias stack) = the boundary of every plane.
+ * octseg_stack_distance: d2 int32 [N][channels][H][W] = the squared distance of every pixel to part `to` of its own plane.
+ * The pair calls take a device list pairs int32 [npairs][2] = (channel of src, channel of dst); for every slice n and pair p, segment
+ * s = n * npairs + p, the QUERY pixels are part src_part of src's plane and the TARGET is part dst_part of dst's plane (src and dst may be the same
+ * stack).  Channel numbers outside their stack are clamped on the device.
+ * octseg_pair_distance_counts: counts int32 [N][npairs][2] = query pixels, target pixels; overlap (may be NULL) int32 [N][npairs][3] =
+ *   |a & b|, |a|, |b| of the two planes' SET pixels whatever the parts, so that Dice and IoU come from the same call.
+ * octseg_pair_distance_keys: for every query pixel of segment s one int64 key = (first_segment + s) << 32 | d2 is stored into
+ *   keys[offsets[s] + slot], offsets device int64 [N * npairs] (the caller's running sum of the query counts), the slots of a segment handed out
+ *   by an integer atomic in no fixed order: sort the keys.  A position outside 0 .. capacity - 1 is NOT stored and sets *overflow (device int32,
+ *   cleared by the caller) to 1: never a store past the buffer.
+ * octseg_pair_distance_min: out uint64 [N][npairs] = the minimum over the segment's query pixels of d2 << 32 | (y * W + x): the smallest squared
+ *   distance and, among the pixels that attain it, the first in raster order; all ones for a segment without query pixels.
+ * Enqueue only, nothing is allocated.  Null pointer (overlap excepted), scratch too small or misaligned, a part outside 0..2, capacity <= 0, out ==
+ * stack: OCTSEG_BAD_ARG; N, H, W <= 0, H or W above 4096 (so that d2 < 2^25 and a column distance fits 16 bits), channels outside 1..16, npairs <= 0,
+ * segment numbers reaching 2^31: OCTSEG_BAD_SHAPE.  Nothing is launched then. */
+#define OCTSEG_DIST_NONE 0x7fffffff
+size_t octseg_distance_scratch_bytes(int N, int H, int W, int channels_a, int channels_b, int pairs);
+int octseg_stack_boundary(const float* stack, int N, int H, int W, int channels, void* scratch, size_t scratch_bytes, float* out, void* stream);
+int octseg_stack_distance(const float* stack, int N, int H, int W, int channels, int to, void* scratch, size_t scratch_bytes, int* d2, void* stream);
+int octseg_pair_distance_counts(const float* src, const float* dst, int N, int H, int W, int channels_a, int channels_b, const int* pairs, int npairs,
+                                int src_part, int dst_part, void* scratch, size_t scratch_bytes, int* counts, int* overlap /* may be NULL */,
+                                void* stream);
+int octseg_pair_distance_keys(const float* src, const float* dst, int N, int H, int W, int channels_a, int channels_b, const int* pairs, int npairs,
+                              int src_part, int dst_part, void* scratch, size_t scratch_bytes, long long first_segment, const long long* offsets,
+                              long long* keys, long long capacity, int* overflow, void* stream);
+int octseg_pair_distance_min(const float* src, const float* dst, int N, int H, int W, int channels_a, int channels_b, const int* pairs, int npairs,
+                             int src_part, int dst_part, void* scratch, size_t scratch_bytes, unsigned long long* out, void* stream);
 
 /* The arithmetic between a DICOM's pixel_array and the frames the pipeline takes (reference src/data/convert_dicoms.py:71-81, repeated in
  * src/app/tools/analysis.py:167-177): per slice cv2.normalize(img, None, alpha=0, beta=255, norm_type=NORM_MINMAX, dtype=CV_8U), then

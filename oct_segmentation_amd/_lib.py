@@ -116,6 +116,15 @@ SYMBOLS = {
     'octseg_components_scratch_bytes': (C.c_size_t, [C.c_int] * 3),
     'octseg_stack_components': (C.c_int, [_P] + [C.c_int] * 4 + [_P, C.c_size_t, _P, _P, _P, _P]),
     'octseg_stack_cleanup': (C.c_int, [_P] + [C.c_int] * 8 + [_P, C.c_size_t, _P, _P, _P, _P]),
+    # float32 mask stacks -> boundary planes, exact squared distance maps, per (slice, channel pair) counts, keyed distance lists and the
+    # minimum with its location (csrc/distance.hip)
+    'octseg_distance_scratch_bytes': (C.c_size_t, [C.c_int] * 6),
+    'octseg_stack_boundary': (C.c_int, [_P] + [C.c_int] * 4 + [_P, C.c_size_t, _P, _P]),
+    'octseg_stack_distance': (C.c_int, [_P] + [C.c_int] * 5 + [_P, C.c_size_t, _P, _P]),
+    'octseg_pair_distance_counts': (C.c_int, [_P, _P] + [C.c_int] * 5 + [_P] + [C.c_int] * 3 + [_P, C.c_size_t, _P, _P, _P]),
+    'octseg_pair_distance_keys': (C.c_int, [_P, _P] + [C.c_int] * 5 + [_P] + [C.c_int] * 3 + [_P, C.c_size_t, C.c_longlong, _P, _P, C.c_longlong,
+                                            _P, _P]),
+    'octseg_pair_distance_min': (C.c_int, [_P, _P] + [C.c_int] * 5 + [_P] + [C.c_int] * 3 + [_P, C.c_size_t, _P, _P]),
     # raw volume [S,H,W,C] uint8 | uint16 -> per-slice min / max + uint8 RGB frames; Pillow's 8-bit bicubic resize from tables (csrc/volume.hip)
     'octseg_volume_normalize': (C.c_int, [_P] + [C.c_int] * 6 + [_P, _P, _P]),
     'octseg_resize_pil_u8': (C.c_int, [_P] + [C.c_int] * 4 + [_P, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, C.c_int, _P]),

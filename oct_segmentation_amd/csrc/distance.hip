@@ -1,0 +1,402 @@
+// distance.hip -- exact Euclidean distance maps of the mask stacks the pipeline carries, and what is read off them: the boundary of every plane,
+// the squared distance of every pixel to the nearest target pixel, the directed boundary-to-boundary distance lists behind the Hausdorff
+// family (HD, HD95, ASSD), the smallest distance between two classes with the pixel that attains it, and the overlap counts of the same
+// planes.  No reference counterpart: the reference reports overlap scores only (DESIGN.md section 5i states the definitions).
+//
+// A plane is one (slice, channel) pair of the float32 stack [N][H][W][C], any value != 0 set.  Planes live as the BIT PLANES of components.hip:
+// row y is W64 = ceil(W / 64) 64-bit words, bit i of word j = pixel 64 j + i, bits past the frame always 0.  Everything is integer arithmetic on
+// SQUARED distances: d2 = dx^2 + dy^2 < 2^25 for H, W <= 4096, exact in int32; no floating point takes part in any decision.  Every phase that
+// needs a grid-wide order is a launch of its own on the caller's stream; no workgroup waits on another, no spin, no cooperative launch.
+//
+//   pack      stack -> bits (the ballot pack of components.hip, kept here as a copy of its own)
+//   part      the plane a call works on, a thread per word: `set` = the plane, `clear` = its complement inside the frame, `boundary` =
+//             m & ~erode(m) with the 4-neighbour cross, outside the frame clear (so a set pixel on the frame edge is boundary): the word ANDed with
+//             the words above and below and with itself shifted by one bit either way, the neighbours' edge bits shifted in.  A word that is not
+//             zero marks its plane as non-empty (every writer stores the same 1).
+//   column    g[y][x] = the vertical distance from (y, x) to the nearest target pixel of column x, uint16, 0xFFFF = none in this column: a thread
+//             per column, one scan down and one up, lanes on consecutive x.  An empty plane is skipped (its g is never read).
+//   row min   d2(y, x) = min over x' of (x - x')^2 + g[y][x']^2, the device function both kernels below share: the row's g staged in LDS (at most
+//             8 KiB), a lane per query pixel, best = g[x]^2, then k = 1, 2, ... testing x - k and x + k until k^2 >= best or both have left the
+//             row.  The loop is bounded by W and best only falls.  O(W) per pixel when the only target sits in a far corner (measured, section 5i).
+//   map       d2 of every pixel of every plane, int32 [N][C][H][W]; DIST_NONE on a plane whose target is empty
+//   count     per (slice, pair): query and target pixels, |a & b|, |a|, |b| of the raw planes; a workgroup per (slice, pair), no atomics
+//   query     d2 of the target plane at the query pixels of the source plane only.  keys: key = (slice * P + pair) << 32 | d2 stored at
+//             offsets[slice * P + pair] + slot, the slot from an integer atomic; a position at or past the capacity is dropped and raises the
+//             overflow flag -- never a store past the buffer.  min: a 64-bit atomicMin of d2 << 32 | (y * W + x) per (slice, pair): the smallest
+//             squared distance and, among the pixels that attain it, the first in raster order.
+//
+// Every index is clamped or guarded: channel numbers of the pair list are clamped into their stacks, slots are checked against the capacity,
+// neighbours outside the frame read as clear.  A wrong argument gives a wrong number, never a stray access.
+#include <algorithm>
+
+#include "common.h"
+#include "kernels.h"
+
+namespace octseg {
+
+namespace {
+
+constexpr int NT = 256, WAVES = NT / 64;
+constexpr unsigned MAX_GRID = 1u << 20;
+constexpr int DIST_NONE = 0x7fffffff;
+constexpr int G_NONE = 0xFFFF;
+constexpr int MAX_W = 4096;
+constexpr int COL_ROWS = 8;
+
+typedef unsigned long long u64;
+typedef unsigned short u16;
+
+struct Geo { int H, W, W64, HW; };
+
+__device__ __forceinline__ u64 inmask(int j, int W) {
+  const int n = W - j * 64;
+  return n >= 64 ? ~0ull : ((1ull << n) - 1ull);
+}
+// word j of row y, 0 outside the frame
+__device__ __forceinline__ u64 rdw(const u64* __restrict__ plane, int y, int j, const Geo& g) {
+  if (y < 0 || y >= g.H || j < 0 || j >= g.W64) return 0ull;
+  return plane[(size_t)y * g.W64 + j];
+}
+
+// min over x' of (x - x')^2 + row[x']^2 for one query pixel; row: the W values of g in LDS.  k^2 and g^2 are below 2^24: the sum fits int32.
+__device__ __forceinline__ int row_min(const u16* row, int W, int x) {
+  const int v = row[x];
+  int best = v == G_NONE ? DIST_NONE : v * v;
+  for (int k = 1; k < W; ++k) {
+    const int k2 = k * k;
+    if (k2 >= best) break;
+    const bool l = x - k >= 0, r = x + k < W;
+    if (!l && !r) break;
+    if (l) { const int a = row[x - k]; if (a != G_NONE) best = min(best, k2 + a * a); }
+    if (r) { const int a = row[x + k]; if (a != G_NONE) best = min(best, k2 + a * a); }
+  }
+  return best;
+}
+
+}  // namespace
+
+// ---- stack <-> bit planes (components.hip's pack / unpack)
+__global__ __launch_bounds__(NT) void dist_pack_kernel(const float* __restrict__ stack, int N, Geo g, int C, u64* __restrict__ bits, int vec) {
+  const int lane = threadIdx.x & 63;
+  const size_t nw = (size_t)gridDim.x * WAVES, total = (size_t)N * g.H * g.W64;
+  for (size_t it = (size_t)blockIdx.x * WAVES + (threadIdx.x >> 6); it < total; it += nw) {     // wave-uniform
+    const int j = (int)(it % g.W64), y = (int)((it / g.W64) % g.H);
+    const size_t n = it / ((size_t)g.W64 * g.H);
+    const int x = j * 64 + lane;
+    const bool ok = x < g.W;
+    const float* px = stack + ((n * g.H + y) * (size_t)g.W + (ok ? x : g.W - 1)) * C;
+    if (vec) {
+      const float4 v = *(const float4*)px;
+      const u64 w0 = __ballot(ok && v.x != 0.f), w1 = __ballot(ok && v.y != 0.f), w2 = __ballot(ok && v.z != 0.f), w3 = __ballot(ok && v.w != 0.f);
+      if (lane < 4) bits[((n * 4 + lane) * g.H + y) * (size_t)g.W64 + j] = lane == 0 ? w0 : lane == 1 ? w1 : lane == 2 ? w2 : w3;
+    } else {
+      for (int c = 0; c < C; ++c) {
+        const u64 w = __ballot(ok && px[c] != 0.f);
+        if (lane == 0) bits[((n * C + c) * g.H + y) * (size_t)g.W64 + j] = w;
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(NT) void dist_unpack_kernel(const u64* __restrict__ bits, int N, Geo g, int C, float* __restrict__ out, int vec) {
+  const int lane = threadIdx.x & 63;
+  const size_t nw = (size_t)gridDim.x * WAVES, total = (size_t)N * g.H * g.W64;
+  for (size_t it = (size_t)blockIdx.x * WAVES + (threadIdx.x >> 6); it < total; it += nw) {
+    const int j = (int)(it % g.W64), y = (int)((it / g.W64) % g.H);
+    const size_t n = it / ((size_t)g.W64 * g.H);
+    const int x = j * 64 + lane;
+    if (x >= g.W) continue;
+    float* px = out + ((n * g.H + y) * (size_t)g.W + x) * C;
+    if (vec) {
+      float4 v;
+      v.x = (float)((bits[((n * 4 + 0) * g.H + y) * (size_t)g.W64 + j] >> lane) & 1ull);
+      v.y = (float)((bits[((n * 4 + 1) * g.H + y) * (size_t)g.W64 + j] >> lane) & 1ull);
+      v.z = (float)((bits[((n * 4 + 2) * g.H + y) * (size_t)g.W64 + j] >> lane) & 1ull);
+      v.w = (float)((bits[((n * 4 + 3) * g.H + y) * (size_t)g.W64 + j] >> lane) & 1ull);
+      *(float4*)px = v;
+    } else {
+      for (int c = 0; c < C; ++c) px[c] = (float)((bits[((n * C + c) * g.H + y) * (size_t)g.W64 + j] >> lane) & 1ull);
+    }
+  }
+}
+
+// ---- the part of every plane a call works on, a thread per word.  part: 0 set, 1 clear, 2 boundary.  any (may be null): any[plane] = 1 when the
+// result holds a pixel; cleared by the caller beforehand
+__global__ __launch_bounds__(NT) void dist_part_kernel(const u64* __restrict__ src, u64* __restrict__ dst, int P, Geo g, int part, int* __restrict__ any) {
+  const size_t total = (size_t)P * g.H * g.W64;
+  for (size_t it = (size_t)blockIdx.x * NT + threadIdx.x; it < total; it += (size_t)gridDim.x * NT) {
+    const int j = (int)(it % g.W64), y = (int)((it / g.W64) % g.H);
+    const size_t pl = it / ((size_t)g.W64 * g.H);
+    const u64* plane = src + pl * g.H * g.W64;
+    const u64 w = src[it];
+    u64 o;
+    if (part == 0) {
+      o = w;
+    } else if (part == 1) {
+      o = ~w & inmask(j, g.W);
+    } else {
+      o = 0ull;
+      if (w) {                                                     // bits past the frame are clear: pixel W - 1 sees a clear right neighbour
+        const u64 prev = rdw(plane, y, j - 1, g), next = rdw(plane, y, j + 1, g);
+        const u64 ero = w & rdw(plane, y - 1, j, g) & rdw(plane, y + 1, j, g) & ((w << 1) | (prev >> 63)) & ((w >> 1) | (next << 63));
+        o = w & ~ero;
+      }
+    }
+    dst[it] = o;
+    if (o && any) any[pl] = 1;
+  }
+}
+
+// ---- column pass, a thread per (plane, column)
+__global__ __launch_bounds__(NT) void dist_column_kernel(const u64* __restrict__ bits, int P, Geo g, const int* __restrict__ any, u16* __restrict__ gcol) {
+  const size_t total = (size_t)P * g.W;
+  for (size_t it = (size_t)blockIdx.x * NT + threadIdx.x; it < total; it += (size_t)gridDim.x * NT) {
+    const int x = (int)(it % g.W);
+    const size_t pl = it / g.W;
+    if (!any[pl]) continue;
+    const u64* col = bits + pl * g.H * g.W64 + (x >> 6);
+    u16* gc = gcol + pl * g.HW + x;
+    const int sh = x & 63;
+    // both scans take COL_ROWS rows at a time, the loads of a group issued before its stores: the up scan reads what the down scan stored
+    // through the same pointer, and a load per row behind a store per row would leave one load in flight per lane
+    int d = G_NONE;
+    for (int y0 = 0; y0 < g.H; y0 += COL_ROWS) {                   // d <= H - 1 <= 4095 wherever it counts
+      u64 wv[COL_ROWS];
+#pragma unroll
+      for (int i = 0; i < COL_ROWS; ++i) wv[i] = col[(size_t)min(y0 + i, g.H - 1) * g.W64];
+#pragma unroll
+      for (int i = 0; i < COL_ROWS; ++i) {
+        if (y0 + i >= g.H) break;
+        if ((wv[i] >> sh) & 1ull) d = 0; else if (d != G_NONE) ++d;
+        gc[(size_t)(y0 + i) * g.W] = (u16)d;
+      }
+    }
+    d = G_NONE;
+    for (int y1 = g.H - 1; y1 >= 0; y1 -= COL_ROWS) {
+      int dn[COL_ROWS];
+#pragma unroll
+      for (int i = 0; i < COL_ROWS; ++i) dn[i] = gc[(size_t)max(y1 - i, 0) * g.W];
+#pragma unroll
+      for (int i = 0; i < COL_ROWS; ++i) {
+        if (y1 - i < 0) break;
+        if (dn[i] == 0) d = 0; else if (d != G_NONE) ++d;
+        if (d < dn[i]) gc[(size_t)(y1 - i) * g.W] = (u16)d;
+      }
+    }
+  }
+}
+
+// ---- full map: a workgroup per (plane, row), the row of g in LDS
+__global__ __launch_bounds__(NT) void dist_map_kernel(const u16* __restrict__ gcol, const int* __restrict__ any, int P, Geo g, int* __restrict__ d2) {
+  __shared__ u16 row[MAX_W];
+  const size_t total = (size_t)P * g.H;
+  for (size_t it = blockIdx.x; it < total; it += gridDim.x) {      // workgroup-uniform
+    const size_t pl = it / g.H;
+    int* out = d2 + it * g.W;
+    if (!any[pl]) {
+      for (int x = threadIdx.x; x < g.W; x += NT) out[x] = DIST_NONE;
+      continue;
+    }
+    const u16* src = gcol + it * g.W;
+    for (int x = threadIdx.x; x < g.W; x += NT) row[x] = src[x];
+    __syncthreads();
+    for (int x = threadIdx.x; x < g.W; x += NT) out[x] = row_min(row, g.W, x);
+    __syncthreads();                                               // the next row overwrites the stage
+  }
+}
+
+// ---- counts: a workgroup per (slice, pair).  counts [N][P][2] = query, target pixels; overlap [N][P][3] = |a & b|, |a|, |b| of the raw planes
+__global__ __launch_bounds__(NT) void dist_count_kernel(const u64* __restrict__ rawa, const u64* __restrict__ rawb, const u64* __restrict__ qbits,
+                                                        const u64* __restrict__ tbits, int N, Geo g, int Ca, int Cb, const int* __restrict__ pairs,
+                                                        int P, int* __restrict__ counts, int* __restrict__ overlap) {
+  __shared__ int red[5][NT];
+  const size_t total = (size_t)N * P, words = (size_t)g.H * g.W64;
+  for (size_t it = blockIdx.x; it < total; it += gridDim.x) {
+    const size_t n = it / P;
+    const int p = (int)(it % P);
+    const int ca = min(max(pairs[2 * p], 0), Ca - 1), cb = min(max(pairs[2 * p + 1], 0), Cb - 1);
+    const size_t oa = (n * Ca + ca) * words, ob = (n * Cb + cb) * words;
+    int s[5] = {0, 0, 0, 0, 0};
+    for (size_t i = threadIdx.x; i < words; i += NT) {
+      const u64 a = rawa[oa + i], b = rawb[ob + i];
+      s[0] += __popcll(qbits[oa + i]);
+      s[1] += __popcll(tbits[ob + i]);
+      s[2] += __popcll(a & b);
+      s[3] += __popcll(a);
+      s[4] += __popcll(b);
+    }
+    for (int k = 0; k < 5; ++k) red[k][threadIdx.x] = s[k];
+    __syncthreads();
+    for (int st = NT >> 1; st > 0; st >>= 1) {
+      if ((int)threadIdx.x < st) for (int k = 0; k < 5; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + st];
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+      counts[it * 2] = red[0][0];
+      counts[it * 2 + 1] = red[1][0];
+      if (overlap) { overlap[it * 3] = red[2][0]; overlap[it * 3 + 1] = red[3][0]; overlap[it * 3 + 2] = red[4][0]; }
+    }
+    __syncthreads();
+  }
+}
+
+// ---- d2 at the query pixels: a workgroup per (slice, pair, row).  keys (with offsets, cursor, capacity, overflow) and / or minout
+__global__ __launch_bounds__(NT) void dist_query_kernel(const u64* __restrict__ qbits, const u16* __restrict__ gcol, const int* __restrict__ any, int N,
+                                                        Geo g, int Ca, int Cb, const int* __restrict__ pairs, int P, long long seg0,
+                                                        const long long* __restrict__ offsets, int* __restrict__ cursor, long long* __restrict__ keys,
+                                                        long long capacity, int* __restrict__ overflow, u64* __restrict__ minout) {
+  __shared__ u16 row[MAX_W];
+  __shared__ u64 qrow[MAX_W / 64];
+  const size_t total = (size_t)N * P * g.H;
+  const int lane = threadIdx.x & 63;
+  for (size_t it = blockIdx.x; it < total; it += gridDim.x) {      // workgroup-uniform
+    const int y = (int)(it % g.H);
+    const size_t seg = it / g.H, n = seg / P;
+    const int p = (int)(seg % P);
+    const int ca = min(max(pairs[2 * p], 0), Ca - 1), cb = min(max(pairs[2 * p + 1], 0), Cb - 1);
+    const size_t pa = n * Ca + ca, pb = n * Cb + cb;
+    u64 mine = 0ull;
+    if ((int)threadIdx.x < g.W64) mine = qbits[(pa * g.H + y) * g.W64 + threadIdx.x];
+    if (!__syncthreads_or(mine != 0ull)) continue;                 // no query pixel in this row
+    if ((int)threadIdx.x < g.W64) qrow[threadIdx.x] = mine;
+    const int have = any[pb];
+    if (have) {
+      const u16* src = gcol + (pb * g.H + y) * (size_t)g.W;
+      for (int x = threadIdx.x; x < g.W; x += NT) row[x] = src[x];
+    }
+    __syncthreads();
+    u64 best = ~0ull;
+    for (int x = threadIdx.x; x < g.W; x += NT) {
+      if (!((qrow[x >> 6] >> (x & 63)) & 1ull)) continue;
+      const int d = have ? row_min(row, g.W, x) : DIST_NONE;
+      if (keys) {
+        const int slot = atomicAdd(cursor + seg, 1);
+        const long long pos = offsets[seg] + slot;
+        if (pos >= 0 && pos < capacity) keys[pos] = (long long)(((u64)(seg0 + (long long)seg) << 32) | (u64)(unsigned)d);
+        else *overflow = 1;
+      }
+      if (minout) {
+        const u64 k = ((u64)(unsigned)d << 32) | (u64)(unsigned)(y * g.W + x);
+        best = k < best ? k : best;
+      }
+    }
+    if (minout) {                                                   // every lane takes part in the shuffles
+      for (int s = 32; s > 0; s >>= 1) {
+        const u64 o = __shfl_xor(best, s, 64);
+        best = o < best ? o : best;
+      }
+      if (lane == 0 && best != ~0ull) atomicMin(minout + seg, best);
+    }
+    __syncthreads();                                               // the next row overwrites the stages
+  }
+}
+
+namespace {
+
+size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+struct Scratch {
+  u64 *rawa, *rawb, *qa, *tb;
+  u16* g;
+  int *any, *cursor;
+  size_t bytes;
+};
+
+// one-stack calls: Cb = 0, pairs = 0 (rawa, qa = the part, g, any over N * Ca planes)
+Scratch carve(void* base, size_t N, int H, int W, int Ca, int Cb, int pairs) {
+  Scratch s;
+  const size_t HW = (size_t)H * W, words = (size_t)H * (((size_t)W + 63) / 64);
+  const size_t Pa = N * Ca, Pb = N * Cb, Pt = Cb ? Pb : Pa;
+  const uintptr_t p = (uintptr_t)base;
+  size_t o = 0;
+  s.rawa = (u64*)(p + o); o += al256(Pa * words * sizeof(u64));
+  s.qa = (u64*)(p + o); o += al256(Pa * words * sizeof(u64));
+  s.rawb = (u64*)(p + o); o += al256(Pb * words * sizeof(u64));
+  s.tb = (u64*)(p + o); o += al256(Pb * words * sizeof(u64));
+  s.g = (u16*)(p + o); o += al256(Pt * HW * sizeof(u16));
+  s.any = (int*)(p + o); o += al256(Pt * sizeof(int));
+  s.cursor = (int*)(p + o); o += al256(N * (size_t)pairs * sizeof(int));
+  s.bytes = o;
+  return s;
+}
+
+Geo geo(int H, int W) { return Geo{H, W, (W + 63) / 64, H * W}; }
+
+unsigned wave_grid(size_t words) { return (unsigned)std::min<size_t>((words + WAVES - 1) / WAVES, MAX_GRID); }
+unsigned item_grid(size_t items) { return (unsigned)std::min<size_t>((items + NT - 1) / NT, MAX_GRID); }
+unsigned block_grid(size_t blocks) { return (unsigned)std::min<size_t>(blocks, MAX_GRID); }
+
+void pack(const float* stack, int N, const Geo& g, int C, u64* bits, hipStream_t st) {
+  const int vec = (C == 4 && ((uintptr_t)stack & 15) == 0) ? 1 : 0;
+  hipLaunchKernelGGL(dist_pack_kernel, dim3(wave_grid((size_t)N * g.H * g.W64)), dim3(NT), 0, st, stack, N, g, C, bits, vec);
+}
+
+// pack both stacks, derive the query planes of src and the target planes of dst (any = which target planes hold a pixel)
+hipError_t prepare_pair(const float* src, const float* dst, int N, const Geo& g, int Ca, int Cb, int src_part, int dst_part, const Scratch& s,
+                        hipStream_t st) {
+  const size_t wa = (size_t)N * Ca * g.H * g.W64, wb = (size_t)N * Cb * g.H * g.W64;
+  pack(src, N, g, Ca, s.rawa, st);
+  pack(dst, N, g, Cb, s.rawb, st);
+  hipError_t e = hipMemsetAsync(s.any, 0, (size_t)N * Cb * sizeof(int), st);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(dist_part_kernel, dim3(item_grid(wa)), dim3(NT), 0, st, s.rawa, s.qa, N * Ca, g, src_part, (int*)nullptr);
+  hipLaunchKernelGGL(dist_part_kernel, dim3(item_grid(wb)), dim3(NT), 0, st, s.rawb, s.tb, N * Cb, g, dst_part, s.any);
+  return hipSuccess;
+}
+
+}  // namespace
+
+size_t distance_scratch_bytes(size_t N, int H, int W, int Ca, int Cb, int pairs) { return carve(nullptr, N, H, W, Ca, Cb, pairs).bytes; }
+
+hipError_t launch_stack_boundary(const float* stack, int N, int H, int W, int C, void* scratch, float* out, hipStream_t st) {
+  const Geo g = geo(H, W);
+  const Scratch s = carve(scratch, N, H, W, C, 0, 0);
+  pack(stack, N, g, C, s.rawa, st);
+  hipLaunchKernelGGL(dist_part_kernel, dim3(item_grid((size_t)N * C * g.H * g.W64)), dim3(NT), 0, st, s.rawa, s.qa, N * C, g, 2, (int*)nullptr);
+  const int vec = (C == 4 && ((uintptr_t)out & 15) == 0) ? 1 : 0;
+  hipLaunchKernelGGL(dist_unpack_kernel, dim3(wave_grid((size_t)N * g.H * g.W64)), dim3(NT), 0, st, s.qa, N, g, C, out, vec);
+  return hipGetLastError();
+}
+
+hipError_t launch_stack_distance(const float* stack, int N, int H, int W, int C, int to, void* scratch, int* d2, hipStream_t st) {
+  const Geo g = geo(H, W);
+  const int P = N * C;
+  const Scratch s = carve(scratch, N, H, W, C, 0, 0);
+  pack(stack, N, g, C, s.rawa, st);
+  hipError_t e = hipMemsetAsync(s.any, 0, (size_t)P * sizeof(int), st);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(dist_part_kernel, dim3(item_grid((size_t)P * g.H * g.W64)), dim3(NT), 0, st, s.rawa, s.qa, P, g, to, s.any);
+  hipLaunchKernelGGL(dist_column_kernel, dim3(item_grid((size_t)P * g.W)), dim3(NT), 0, st, s.qa, P, g, s.any, s.g);
+  hipLaunchKernelGGL(dist_map_kernel, dim3(block_grid((size_t)P * g.H)), dim3(NT), 0, st, s.g, s.any, P, g, d2);
+  return hipGetLastError();
+}
+
+hipError_t launch_pair_distance_counts(const float* src, const float* dst, int N, int H, int W, int Ca, int Cb, const int* pairs, int P, int src_part,
+                                       int dst_part, void* scratch, int* counts, int* overlap, hipStream_t st) {
+  const Geo g = geo(H, W);
+  const Scratch s = carve(scratch, N, H, W, Ca, Cb, P);
+  hipError_t e = prepare_pair(src, dst, N, g, Ca, Cb, src_part, dst_part, s, st);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(dist_count_kernel, dim3(block_grid((size_t)N * P)), dim3(NT), 0, st, s.rawa, s.rawb, s.qa, s.tb, N, g, Ca, Cb, pairs, P, counts,
+                     overlap);
+  return hipGetLastError();
+}
+
+// keys and / or minout (the other null)
+hipError_t launch_pair_distance_query(const float* src, const float* dst, int N, int H, int W, int Ca, int Cb, const int* pairs, int P, int src_part,
+                                      int dst_part, void* scratch, long long seg0, const long long* offsets, long long* keys, long long capacity,
+                                      int* overflow, unsigned long long* minout, hipStream_t st) {
+  const Geo g = geo(H, W);
+  const Scratch s = carve(scratch, N, H, W, Ca, Cb, P);
+  hipError_t e = prepare_pair(src, dst, N, g, Ca, Cb, src_part, dst_part, s, st);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(dist_column_kernel, dim3(item_grid((size_t)N * Cb * g.W)), dim3(NT), 0, st, s.tb, N * Cb, g, s.any, s.g);
+  if (keys) e = hipMemsetAsync(s.cursor, 0, (size_t)N * P * sizeof(int), st);
+  if (e == hipSuccess && minout) e = hipMemsetAsync(minout, 0xFF, (size_t)N * P * sizeof(unsigned long long), st);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(dist_query_kernel, dim3(block_grid((size_t)N * P * g.H)), dim3(NT), 0, st, s.qa, s.g, s.any, N, g, Ca, Cb, pairs, P, seg0, offsets,
+                     s.cursor, keys, capacity, overflow, (u64*)minout);
+  return hipGetLastError();
+}
+
+}  // namespace octseg

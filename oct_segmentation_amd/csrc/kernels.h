@@ -358,6 +358,18 @@ hipError_t launch_stack_components(const float* stack, int N, int H, int W, int 
 hipError_t launch_stack_cleanup(const float* stack, int N, int H, int W, int C, int smooth_k, int keep, int min_area, int fill_holes, void* scratch,
                                 float* out, int* ncomp, int* top, hipStream_t st);
 
+// boundary distances (distance.hip): the boundary of every plane, the exact squared Euclidean distance map (column pass + row minimum in LDS), and
+// per (slice, pair of channels) the counts, the keyed list of d2 at the query pixels, and their minimum with its location.  scratch:
+// distance_scratch_bytes(N, H, W, Ca, Cb, pairs) device bytes (one-stack calls: Cb = 0, pairs = 0).  part / to: 0 set, 1 clear, 2 boundary
+size_t distance_scratch_bytes(size_t N, int H, int W, int Ca, int Cb, int pairs);
+hipError_t launch_stack_boundary(const float* stack, int N, int H, int W, int C, void* scratch, float* out, hipStream_t st);
+hipError_t launch_stack_distance(const float* stack, int N, int H, int W, int C, int to, void* scratch, int* d2, hipStream_t st);
+hipError_t launch_pair_distance_counts(const float* src, const float* dst, int N, int H, int W, int Ca, int Cb, const int* pairs, int P, int src_part,
+                                       int dst_part, void* scratch, int* counts, int* overlap, hipStream_t st);
+hipError_t launch_pair_distance_query(const float* src, const float* dst, int N, int H, int W, int Ca, int Cb, const int* pairs, int P, int src_part,
+                                      int dst_part, void* scratch, long long seg0, const long long* offsets, long long* keys, long long capacity,
+                                      int* overflow, unsigned long long* minout, hipStream_t st);
+
 // raw pullback volumes (volume.hip): per-slice min / max + cv2.normalize(NORM_MINMAX, CV_8U) + channel order into uint8 [S][H][W][3] (one init,
 // two launches), and Pillow's 8-bit two-pass resample from host tables (a launch per axis that changes length; a copy when none does)
 hipError_t launch_volume_normalize(const void* src, int src_u16, int S, int H, int W, int C, int swap_rb, unsigned* minmax, uint8_t* dst,

@@ -6,7 +6,8 @@
 // encoder pair at the smallest legal frame, the benchmark frame and a non-square one, in all three dtypes, with no kernel launched
 // (no GPU needed).  A subset of the plans is then driven through octseg_net_forward / _backward / _backward_sliced / octseg_optim_step and
 // the graph-captured eval forward, and the class-activation-map path (frozen forward, seeded backward, map launches) against tools/hip_host_stubs.cpp, a recording stand-in for the HIP runtime that checks every launch
-// geometry and every memset / copy range.  Exit code 0 = the sanitizers and the stubs saw nothing.
+// geometry and every memset / copy range; the boundary-distance entry points (csrc/distance.hip) are driven the same way, from a 1 x 1 frame to
+// 4096 x 4096.  Exit code 0 = the sanitizers and the stubs saw nothing.
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -106,6 +107,56 @@ int exercise(const octseg_net_desc& d, octseg_plan* p) {
   }
   return 0;
 }
+
+// The boundary-distance entry points (csrc/distance.hip, csrc/distance_api.cpp) against the stubs: the scratch carving, the three memsets
+// (non-empty flags, slot cursors, minima) inside their ranges and every grid, from a 1 x 1 frame to the largest one the calls take; then
+// what they must refuse.
+int exercise_distance() {
+  char* base = (char*)(uintptr_t)0x200000000000ull;
+  auto carve = [&](size_t bytes) { char* r = base; base += (bytes + 4095) / 4096 * 4096 + 4096; dry_register_range(r, bytes); return r; };
+  const int shapes[][4] = {{1, 1, 1, 1}, {3, 97, 130, 5}, {186, 750, 750, 4}, {2, 4096, 4096, 16}};
+  const int P = 7;
+  for (auto& sh : shapes) {
+    dry_clear_ranges();
+    const int N = sh[0], H = sh[1], W = sh[2], C = sh[3];
+    const size_t one = octseg_distance_scratch_bytes(N, H, W, C, 0, 0), two = octseg_distance_scratch_bytes(N, H, W, C, C, P);
+    if (one == 0 || two <= one) return 30;
+    const size_t elems = (size_t)N * H * W * C;
+    float* a = (float*)carve(elems * 4);
+    float* b = (float*)carve(elems * 4);
+    float* out = (float*)carve(elems * 4);
+    int* d2 = (int*)carve(elems * 4);
+    void* scratch = carve(two);
+    int* pairs = (int*)carve(P * 2 * 4);
+    int* counts = (int*)carve((size_t)N * P * 2 * 4);
+    int* overlap = (int*)carve((size_t)N * P * 3 * 4);
+    long long* offsets = (long long*)carve((size_t)N * P * 8);
+    long long* keys = (long long*)carve(1024 * 8);
+    int* overflow = (int*)carve(4);
+    unsigned long long* minima = (unsigned long long*)carve((size_t)N * P * 8);
+    void* st = (void*)(uintptr_t)0x5000;
+    if (octseg_stack_boundary(a, N, H, W, C, scratch, one, out, st) != 0) { fprintf(stderr, "stack_boundary: %s\n", octseg_last_error()); return 31; }
+    for (int to = 0; to < 3; ++to)
+      if (octseg_stack_distance(a, N, H, W, C, to, scratch, one, d2, st) != 0) { fprintf(stderr, "stack_distance: %s\n", octseg_last_error()); return 32; }
+    if (octseg_pair_distance_counts(a, b, N, H, W, C, C, pairs, P, 2, 2, scratch, two, counts, overlap, st) != 0) return 33;
+    if (octseg_pair_distance_counts(a, a, N, H, W, C, C, pairs, P, 0, 1, scratch, two, counts, nullptr, st) != 0) return 33;
+    if (octseg_pair_distance_keys(a, b, N, H, W, C, C, pairs, P, 2, 2, scratch, two, 5, offsets, keys, 1024, overflow, st) != 0) return 34;
+    if (octseg_pair_distance_min(a, b, N, H, W, C, C, pairs, P, 0, 0, scratch, two, minima, st) != 0) return 35;
+    // refused before anything is enqueued
+    const unsigned long long before = dry_launches() + dry_memops();
+    if (octseg_stack_distance(a, N, H, W, C, 0, scratch, one - 1, d2, st) == 0 || octseg_stack_distance(a, N, H, 4097, C, 0, scratch, one, d2, st) == 0 ||
+        octseg_stack_distance(a, N, H, W, 17, 0, scratch, one, d2, st) == 0 || octseg_stack_distance(a, N, H, W, C, 3, scratch, one, d2, st) == 0 ||
+        octseg_stack_boundary(a, N, H, W, C, scratch, one, a, st) == 0 ||
+        octseg_pair_distance_counts(a, b, N, H, W, C, C, pairs, P, 2, 2, scratch, two - 1, counts, overlap, st) == 0 ||
+        octseg_pair_distance_keys(a, b, N, H, W, C, C, pairs, P, 2, 2, scratch, two, 0, offsets, keys, 0, overflow, st) == 0 ||
+        octseg_pair_distance_keys(a, b, N, H, W, C, C, pairs, P, 2, 2, scratch, two, (1ll << 31) - 1, offsets, keys, 1024, overflow, st) == 0 ||
+        octseg_pair_distance_min(a, b, N, H, W, C, C, pairs, 0, 0, 0, scratch, two, minima, st) == 0)
+      return 36;
+    if (dry_launches() + dry_memops() != before) { fprintf(stderr, "a refused distance call enqueued work\n"); return 37; }
+  }
+  if (octseg_distance_scratch_bytes(1, 4097, 8, 1, 0, 0) != 0 || octseg_distance_scratch_bytes(1, 8, 8, 17, 0, 0) != 0) return 38;
+  return 0;
+}
 }  // namespace
 
 int main() {
@@ -200,6 +251,7 @@ int main() {
   for (octseg_net_desc* b : {&bad1, &bad2, &bad3, &bad4, &bad5})
     if (octseg_plan_create(b, &q) == 0) { fprintf(stderr, "a bad descriptor was accepted\n"); return 7; }
   for (int dt = 0; dt < 3; ++dt) checksum += octseg_conv2d_scratch_bytes(dt, 2, 64, 64, 24, 40, 3, 3) + octseg_conv2d_scratch_bytes(dt, 1, 8, 8, 2048, 512, 1, 1);
+  if (const int rc = exercise_distance()) { fprintf(stderr, "exercise_distance -> %d\n", rc); return rc; }
   if (dry_errors() != 0) { fprintf(stderr, "%llu launch / memory-range violations\n", dry_errors()); return 8; }
   printf("plan_dryrun: %d plans built, %d of them run through forward / backward / optimizer with recording HIP stubs (%llu launches, %llu memory "
          "operations checked) under ASan + UBSan, checksum %llu, 0 errors, launch fingerprint %016llx\n", plans, executed, dry_launches(), dry_memops(), checksum,
