@@ -516,7 +516,10 @@ template <int RB> struct ConvCfg { static constexpr int PITCH = RB + 16, KSTEPS 
 //                                 22^2 map of a 704^2 frame -- whose 16-pixel tiling ends in a nearly empty round (44^2 at 16 frames: 288 workgroups
 //                                 on 256 CUs; here 512 on 512 slots) or half-empty tiles (22^2: 47 % -> 94.5 %)
 //                               7 masked, on 11 x 11 pixel tiles (the tied data gradient over the 44^2 / 22^2 low-resolution maps)
-enum { LOOP_GENERIC = 0, LOOP_RESIDENT = 1, LOOP_1X1 = 2, LOOP_RUN9 = 3, LOOP_RUN9S = 4, LOOP_MASKED = 5, LOOP_T11 = 6, LOOP_MASKED_T11 = 7 };
+//                               8 run9p (3x3, several K chunks, 16 x 16 pixels x 64 channels on four waves of 64 x 64): loop 6's form on the 16-pixel
+//                                 tiling -- ONE window buffer, the next chunk's 18 x 18 window (eleven passes) prefetched into registers over the nine
+//                                 taps (2 + 2 + 7 x 1), two workgroups per CU: the 33..64-channel decoder layers over 320..896 input channels
+enum { LOOP_GENERIC = 0, LOOP_RESIDENT = 1, LOOP_1X1 = 2, LOOP_RUN9 = 3, LOOP_RUN9S = 4, LOOP_MASKED = 5, LOOP_T11 = 6, LOOP_MASKED_T11 = 7, LOOP_RUN9P = 8 };
 
 template <typename T, int NT, int WN, int WM, int RB, int LOOP>
 __global__ __launch_bounds__(64 * WM * WN, ((WM * WN == 4 && wave_mt(NT, RB) == 2) ? 2 : 1)) void conv_mfma_kernel(const ConvArgs a, const int mode) {
@@ -891,8 +894,9 @@ __global__ __launch_bounds__(64 * WM * WN, ((WM * WN == 4 && wave_mt(NT, RB) == 
   };
   // LOOP_T11: the rolled loop with ONE window buffer, the next chunk's window (six passes of a 13 x 13 window) loaded into registers one pass
   // per tap and stored in place behind the chunk's last barrier -- the loads' latency sits under the chunk's MFMAs instead of in front of the next
+  // LOOP_RUN9P: the same loop on the 16 x 16-pixel tile, whose 18 x 18 window is eleven passes of 32 pixels -- taps 0 and 1 load two passes each
   auto run_t11 = [&](auto np_c) {
-    constexpr int NP = decltype(np_c)::value;   // window passes (host: npass <= NP <= ntaps)
+    constexpr int NP = decltype(np_c)::value;   // window passes (host: npass <= NP <= 18); tap t loads (NP + 8 - t) / 9 of them: 6 = 6 x 1, 11 = 2 + 2 + 7 x 1
     int it = 0;
     int tap2 = 1, chunk2 = 0;
     for (int chunk = 0; chunk < nchunks; ++chunk) {
@@ -903,10 +907,12 @@ __global__ __launch_bounds__(64 * WM * WN, ((WM * WN == 4 && wave_mt(NT, RB) == 
       uint4 av[NP];
       bool aok[NP];
       int hy = hy_first, hx = hx_first, hp = p0w;
+      int pi = 0;   // (both loops are unrolled: a constant)
 #pragma unroll
       for (int t = 0; t < 9; ++t, ++it) {
-        if (t < NP) {
-          av[t] = nxt.load_at(hy, hx, hp < npix, gy0, gx0, smul, IHl, IWl, aok[t]);
+#pragma unroll
+        for (int u = 0; u < (NP + 8 - t) / 9; ++u, ++pi) {
+          av[pi] = nxt.load_at(hy, hx, hp < npix, gy0, gx0, smul, IHl, IWl, aok[pi]);
           const bool adv = hp + Stager::PSTEP < npass * Stager::PSTEP;
           if (adv) {
             hp += Stager::PSTEP;
@@ -1325,6 +1331,8 @@ __global__ __launch_bounds__(64 * WM * WN, ((WM * WN == 4 && wave_mt(NT, RB) == 
     run1p();   // (the rolled loop is not kept as an A/B switch here: with both in one function hipcc moved the by-value ConvArgs to scratch)
   } else if constexpr (LOOP == LOOP_T11) {   // host-checked: nine taps, one window buffer, six window passes
     run_t11(std::integral_constant<int, 6>{});
+  } else if constexpr (LOOP == LOOP_RUN9P) {   // host-checked: nine taps, one window buffer, eleven window passes
+    run_t11(std::integral_constant<int, 11>{});
   } else {
     if (dbuf) run(std::integral_constant<int, 1>{}, std::true_type{});
     else run(std::integral_constant<int, 1>{}, std::false_type{});
@@ -1383,7 +1391,14 @@ hipError_t launch_loop(const ConvArgs& a, int mode, size_t lds, hipStream_t st) 
 
 template <typename T, int NT, int WN, int WM, int RB>
 hipError_t launch_variant(const ConvArgs& a, int mode, int loop, size_t lds, hipStream_t st) {
+  if constexpr (NT == 2 && WN == 1) {   // four waves of 64 pixels x 64 channels on a 64-channel N tile: choose() gives it 2-byte 3x3 layers on run9p only
+    if constexpr (sizeof(T) == 2 && WM == 4 && RB == 128) {
+      if (loop == LOOP_RUN9P) return launch_loop<T, NT, WN, WM, RB, LOOP_RUN9P>(a, mode, lds, st);
+    }
+    return hipErrorInvalidValue;
+  } else
   switch (loop) {
+    case LOOP_RUN9P: return hipErrorInvalidValue;
     case LOOP_RESIDENT: return launch_loop<T, NT, WN, WM, RB, LOOP_RESIDENT>(a, mode, lds, st);
     case LOOP_1X1: return launch_loop<T, NT, WN, WM, RB, LOOP_1X1>(a, mode, lds, st);
     case LOOP_RUN9:
@@ -1407,7 +1422,7 @@ hipError_t launch_variant(const ConvArgs& a, int mode, int loop, size_t lds, hip
 
 // Tile choice: N tile from Cout, K chunk from Cin, M tile (16x16 or 8x16 pixels) from tile utilisation
 // and LDS fit (double-buffered window preferred).
-struct Choice { Variant v; int dbuf; size_t lds; int resident; int ring3; int ring1; int tile11; };   // ring3: run9r, ring1: run9s (one chunk)
+struct Choice { Variant v; int dbuf; size_t lds; int resident; int ring3; int ring1; int tile11; int rp11; };   // ring3: run9r, ring1: run9s (one chunk), rp11: run9p
 
 // LOOP_T11's launches: 2-byte 3x3 stride-1 layers with > 64 output channels on maps that are multiples of 11 and not of 16, up to 88 pixels a
 // side, whose 16-pixel tiling is a grid of at most 4608 workgroups (U-Net++/resnet101 16 x 704^2, ms per step of the MFMA kernels alone: off 58.74,
@@ -1444,7 +1459,7 @@ static bool any_pooled_dst(const ConvArgs& a) {
 
 static Choice choose(const ConvArgs& a, int esz) {
   Choice c;
-  c.ring3 = 0; c.ring1 = 0; c.tile11 = 0;
+  c.ring3 = 0; c.ring1 = 0; c.tile11 = 0; c.rp11 = 0;
   const bool t11 = tile11_geom(a, esz);
   if (t11 && !any_pooled_dst(a)) {
     c.v = Variant{2, 2, 2, 128}; c.dbuf = 0; c.resident = 0; c.tile11 = 1; c.lds = lds_single128(esz);
@@ -1518,6 +1533,7 @@ static Choice choose(const ConvArgs& a, int esz) {
   // tiles number fewer than half the CUs runs at the speed of ONE workgroup's loop (U-Net++/resnet101 at 2 frames per GPU: x_0_0.conv1,
   // 3072 -> 256 @44^2, is 36 workgroups of 27648-deep contractions: 166 TFLOP/s).  A 64-channel N tile and the 8x16-pixel M tile
   // quadruple the workgroup count at the price of slab reuse, which an under-filled chip does not miss.
+  const bool n64 = NT == 1 && WN == 2;   // a 64-channel N tile by the channel counts alone (not by the small-grid rule below)
   bool small_grid = false;
   {
     const int bn = NT * 32 * WN;
@@ -1527,6 +1543,22 @@ static Choice choose(const ConvArgs& a, int esz) {
   }
   const int kc128 = 128 / esz;
   const int RB = a.Cin <= kc128 / 2 ? 64 : 128;
+  // 64-channel N tiles of the 2-byte 3x3 stride-1 layers over SEVERAL 128-byte K chunks (33..64 output channels: U-Net++ x_k_3 / x_0_2 conv1,
+  // 320..896 -> 64): 16 x 16 pixels on four waves of 64 pixels x 64 channels (NT = 2, WN = 1), two workgroups per CU, on run9p.  The 2 x 2 waves of
+  // 64 x 32 on run9r it replaces read 4 A + 2 B fragments per 8 MFMAs and every A row twice (once per wave column), and stage a window per 128
+  // pixels; this wave tile reads 4 + 4 per 16 and stages one per 256.  Measured at 16 x 352^2 in bf16, ABAB on one box (profiles/n64_tile_ab.txt):
+  // forward 448 -> 64 1.286 -> 1.040 ms (796 -> 984 TFLOP/s), 384 -> 64 1.136 -> 0.925, 320 -> 64 0.977 -> 0.792; per MFMA 0.85 -> 0.57 LDS,
+  // 4.4 -> 2.5 vector, 1.8 -> 0.93 scalar instructions, LDS array busy 51 % -> 38 % of the launch.  ONE K chunk (64 -> 64, the K = 64 data
+  // gradients) keeps the 32-channel wave columns: the same wave tile on run9s won the bare launch (192 <- 64 0.750 -> 0.622 ms, 64 -> 64
+  // 0.235 -> 0.228) and lost 3-6 % inside the network (lazy-BN sources, several accumulated destinations: x_1_3.conv1 dgrad 1.185 -> 1.223 ms,
+  // x_k_3.conv2 forward 0.209 -> 0.217), so it is not instantiated.
+  if (n64 && esz == 2 && a.Cin > kc128 && a.ntaps == 9 && a.span_x == 3 && a.span_y == 3 && a.istride == 1 && a.ostride == 1 && a.ooy == 0 && a.oox == 0 &&
+      a.out_mode != OUT_HEAD_NCHW) {
+    const Variant v{2, 1, 4, 128};
+    int npass = 0;
+    const size_t lds = variant_lds(a, v, esz, 0, &npass);
+    if (npass <= 11) { c.v = v; c.dbuf = 0; c.resident = 0; c.rp11 = 1; c.lds = lds; return c; }
+  }
   auto util = [&](int TH) {
     const double ty = (a.OH + TH - 1) / TH, tx = (a.OW + TW - 1) / TW;
     return (double)a.OH * a.OW / (ty * TH * tx * TW);
@@ -1544,8 +1576,9 @@ static Choice choose(const ConvArgs& a, int esz) {
     // ... except the square 64 -> 64 3x3 layers (one N tile): the 16x16 tile measured 3-10 % faster there; the K-thin
     // dgrads of the wide concat layers (several N tiles) keep the small tile (15 % faster)
     if (a.ntaps == 9 && a.Cin <= kc && a.Cout <= 64 && WN > 1) wm_first = 4;
-    // 33..64 output channels over several K chunks (U-Net++ x_k_3 / x_0_2 conv1: 320..896 -> 64): 8x16 tiles, two
-    // workgroups per CU, measured 7-15 % faster than one 8-wave workgroup (its waves own a single 32-channel column)
+    // 33..64 output channels over several K chunks where the 64 x 64 wave tile above does not apply (f32, stride 2): 8x16 tiles, two workgroups
+    // per CU, of waves that own a single 32-channel column (the 2-byte stride-1 layers -- U-Net++ x_k_3 / x_0_2 conv1, 320..896 -> 64 -- left this
+    // form for the one above: +24 %)
     if (a.ntaps == 9 && a.Cin > kc && WN == 2 && NT == 1) wm_first = 2;
     // a 16x16 grid that fits the chip in one round beats more, smaller tiles (layer4 3x3 at 22x22: 256 workgroups, 25 % faster)
     if (a.ntaps == 9 && a.Cin > kc) {
@@ -1608,13 +1641,14 @@ hipError_t dispatch(const ConvArgs& a_in, hipStream_t st) {
       if (a.src[i].c0 % KC != 0) a.src_uniform = 0;
   }
   const int loop = a.taps_per_src > 0 ? (c.tile11 ? LOOP_MASKED_T11 : LOOP_MASKED) : c.tile11 == 3 ? LOOP_MASKED : c.tile11 ? LOOP_T11
-                   : c.resident ? LOOP_RESIDENT : (c.ring3 ? LOOP_RUN9 : (c.ring1 ? LOOP_RUN9S : ((a.ntaps == 1 && c.dbuf) ? LOOP_1X1 : LOOP_GENERIC)));
+                   : c.rp11 ? LOOP_RUN9P : c.resident ? LOOP_RESIDENT : (c.ring3 ? LOOP_RUN9 : (c.ring1 ? LOOP_RUN9S : ((a.ntaps == 1 && c.dbuf) ? LOOP_1X1 : LOOP_GENERIC)));
 #define OCTSEG_CASE(NT_, WN_, WM_, RB_)                                             \
   if (v.NT == NT_ && v.WN == WN_ && v.WM == WM_ && v.RB == RB_)                     \
     return launch_variant<T, NT_, WN_, WM_, RB_>(a, c.dbuf, loop, c.lds, st);
   OCTSEG_CASE(4, 2, 2, 64)
   OCTSEG_CASE(2, 2, 4, 128)
   OCTSEG_CASE(2, 2, 2, 128)
+  OCTSEG_CASE(2, 1, 4, 128)
   OCTSEG_CASE(1, 2, 4, 128)
   OCTSEG_CASE(1, 2, 2, 128)
   OCTSEG_CASE(1, 1, 4, 128)
