@@ -653,6 +653,65 @@ typedef enum {
 int octseg_sweep_op(int op, int dtype, const void* const* ptrs, int nptrs, const long long* iargs, int niargs, const double* fargs,
                     int nfargs, void* stream);
 
+/* ---- single-stage door to the PAN pyramid (csrc/pan.hip) and the MAnet position attention (csrc/pab.hip); csrc/block_api.cpp, wrappers in
+ * blockops.py ----
+ * One call = ONE launcher of csrc/kernels.h on `stream` (IN_BWD: the launcher's two kernels; PYR_BWD: the launcher's memset of gscratch and its
+ * kernel).  T = `dtype`; f = float32 whatever the dtype.  A stage reads only the fields listed for it.  Buffer sizes are the caller's contract
+ * (blockops.py derives every one of them); the door checks what it can see.
+ *   MAXPOOL2_FWD   x T[N][H][W][C] -> p T[N][H/2][W/2][C]                                 (16-byte vectors: C % vec == 0, H and W even)
+ *   MAXPOOL2_BWD   train. x, dp T[N][H/2][W/2][C] -> dx T[N][H][W][C]: the first maximum in scan order takes dp, the others 0; accum: dx +=
+ *   IN_FWD         p T[N][H][W][C], w f[K*K][C], b f[1] -> y f[N][H][W]                   (K x K conv to one channel, pad K / 2; K odd, <= 15)
+ *   IN_BWD         train. p, dy f[N][H][W], w -> dp T[N][H][W][C] (stored), dw f[K*K][C] and db f[1] (accumulated)
+ *   PYR_FWD        the one-channel pyramid below an H x W map (H / 8 >= 1, W / 8 >= 1): x1raw = scratch[0 .. N (H/2) (W/2)) -> every
+ *                  intermediate in `scratch` (layout: pan.hip / blockops.fpa_scratch_views), uu f[N][H][W] at scratch + octseg_fpa_uu_offset().
+ *                  Layers l = 0..5 = down1, down2, down3.1, down3.2, conv2, conv1: pw[l] f[k*k] and pb[l] f[1] for l >= 1 (layer 0's conv is IN_FWD),
+ *                  pg[l], pbe[l], prm[l], prv[l] f[1].  train = 1: batch statistics (running statistics updated, 12 statistics kept); 0: running ones
+ *   PYR_BWD        train. scratch as PYR_FWD(train = 1) left it, duu f[N][H][W] -> gscratch (zeroed here; d x1raw at gscratch + N (H/2) (W/2)),
+ *                  pdw[l], pdb[l] (l >= 1), pdg[l], pdbe[l] accumulated; reads pw[l] (l >= 1), pg[l]
+ *   MIX_FWD        uu f[N][HW], mid T[N][HW][C], b1 T[N][C] -> out T[N][HW][C] = uu mid + b1        (HW = H * W of the descriptor)
+ *   MIX_BWD        train. uu, mid, g T[N][HW][C] -> dmid T[N][HW][C] = g uu, duu f[N][HW] = sum_c g mid
+ *   PAB GEMM       octseg_pab_gemm verbatim (the launcher's PabGemm): C[b][m][n] (+)= sum_k A[b][m][k] B[b][k][n], strides in elements, *_f32: the
+ *                  operand is float whatever the dtype; numelA / numelB / numelC: the elements of the three buffers
+ *   PAB SOFTMAX_FWD  S f[batch][n]: softmax over ALL n entries of each image, in place
+ *   PAB SOFTMAX_BWD  train. S = dP f[batch][n] -> P (dP - sum P dP) in place; P f[batch][n] is only read
+ *   PAB MIX_FWD    x T[N][HW][C], M f[N][HW * C] -> y = x + M read as [C][HW] (the un-transposed reshape)
+ *   PAB MIX_BWD    train. dy T[N][HW][C] -> dM f[N][HW * C] (the same index map)
+ * Refused before any launch: unknown stage, null descriptor, a null required pointer, a pointer not aligned to its element (16 bytes for
+ * maxpool2's tensors), scratch_floats / gscratch_floats below octseg_fpa_scratch_floats() / octseg_fpa_gscratch_floats(): OCTSEG_BAD_ARG;
+ * f16 on a stage marked "train": OCTSEG_BAD_DTYPE; an empty tensor, C % vec != 0 or odd H / W for maxpool2, H / 8 < 1 or W / 8 < 1 for the
+ * pyramid, K even or above 15, batch > 65535, n == 0, a tensor of 2^31 elements or more, train with N (H/8) (W/8) <= 1 ("Expected more than 1
+ * value per channel when training ..."), a GEMM whose largest reachable index of A, B or C lies beyond numelA / numelB / numelC:
+ * OCTSEG_BAD_SHAPE. */
+typedef enum { OCTSEG_FPA_MAXPOOL2_FWD = 0, OCTSEG_FPA_MAXPOOL2_BWD, OCTSEG_FPA_IN_FWD, OCTSEG_FPA_IN_BWD, OCTSEG_FPA_PYR_FWD, OCTSEG_FPA_PYR_BWD,
+               OCTSEG_FPA_MIX_FWD, OCTSEG_FPA_MIX_BWD, OCTSEG_FPA_NUM_STAGES } octseg_fpa_stage;
+typedef struct {
+  int N, H, W, C, K, train, accum;
+  const void* x; void* p; void* dp; void* dx;                              /* MAXPOOL2_* (writes p | reads dp), IN_* (reads p | writes dp) */
+  const float* w; const float* b; float* y; const float* dy; float* dw; float* db;      /* IN_* */
+  float* scratch; size_t scratch_floats; float* gscratch; size_t gscratch_floats;       /* PYR_* */
+  const float* pw[6]; const float* pb[6]; const float* pg[6]; const float* pbe[6]; float* prm[6]; float* prv[6];
+  float* pdw[6]; float* pdb[6]; float* pdg[6]; float* pdbe[6];
+  const float* uu; float* duu;                                             /* MIX_* (duu: also PYR_BWD's input) */
+  const void* mid; const void* b1; void* out; const void* g; void* dmid;
+} octseg_fpa_desc;
+size_t octseg_fpa_scratch_floats(int N, int H, int W);    /* 0 where the pyramid refuses the map */
+size_t octseg_fpa_gscratch_floats(int N, int H, int W);
+size_t octseg_fpa_uu_offset(int N, int H, int W);         /* floats from scratch to uu; the 12 statistics follow uu */
+int octseg_fpa_op(int stage, int dtype, const octseg_fpa_desc* desc, void* stream);
+
+typedef enum { OCTSEG_PAB_GEMM = 0, OCTSEG_PAB_SOFTMAX_FWD, OCTSEG_PAB_SOFTMAX_BWD, OCTSEG_PAB_MIX_FWD, OCTSEG_PAB_MIX_BWD, OCTSEG_PAB_NUM_STAGES } octseg_pab_stage;
+typedef struct {
+  const void* A; const void* B; void* C;
+  size_t sAb, sAm, sAk, sBb, sBk, sBn, sCb, sCm, sCn;
+  int M, N, K, batch, a_f32, b_f32, c_f32, accum;
+} octseg_pab_gemm;
+typedef struct {
+  octseg_pab_gemm gemm; size_t numelA, numelB, numelC;                     /* GEMM */
+  float* S; const float* P; int batch; size_t n;                           /* SOFTMAX_* */
+  const void* x; const float* M; void* y; float* dM; const void* dy; int N, HW, C;      /* MIX_* */
+} octseg_pab_desc;
+int octseg_pab_op(int stage, int dtype, const octseg_pab_desc* desc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -67,6 +67,30 @@ class ConvLayerDesc(C.Structure):   # octseg_conv_layer_desc
                 ('scratch_bytes', C.c_size_t)]
 
 
+_PF6 = C.c_void_p * 6
+
+
+class FpaDesc(C.Structure):   # octseg_fpa_desc
+    _fields_ = ([(k, C.c_int) for k in ('N', 'H', 'W', 'C', 'K', 'train', 'accum')] +
+                [(k, C.c_void_p) for k in ('x', 'p', 'dp', 'dx', 'w', 'b', 'y', 'dy', 'dw', 'db')] +
+                [('scratch', C.c_void_p), ('scratch_floats', C.c_size_t), ('gscratch', C.c_void_p), ('gscratch_floats', C.c_size_t)] +
+                [(k, _PF6) for k in ('pw', 'pb', 'pg', 'pbe', 'prm', 'prv', 'pdw', 'pdb', 'pdg', 'pdbe')] +
+                [(k, C.c_void_p) for k in ('uu', 'duu', 'mid', 'b1', 'out', 'g', 'dmid')])
+
+
+class PabGemm(C.Structure):   # octseg_pab_gemm (= the launcher's PabGemm)
+    _fields_ = ([(k, C.c_void_p) for k in ('A', 'B', 'C')] +
+                [(k, C.c_size_t) for k in ('sAb', 'sAm', 'sAk', 'sBb', 'sBk', 'sBn', 'sCb', 'sCm', 'sCn')] +
+                [(k, C.c_int) for k in ('M', 'N', 'K', 'batch', 'a_f32', 'b_f32', 'c_f32', 'accum')])
+
+
+class PabDesc(C.Structure):   # octseg_pab_desc
+    _fields_ = [('gemm', PabGemm), ('numelA', C.c_size_t), ('numelB', C.c_size_t), ('numelC', C.c_size_t),
+                ('S', C.c_void_p), ('P', C.c_void_p), ('batch', C.c_int), ('n', C.c_size_t),
+                ('x', C.c_void_p), ('M', C.c_void_p), ('y', C.c_void_p), ('dM', C.c_void_p), ('dy', C.c_void_p), ('N', C.c_int), ('HW', C.c_int),
+                ('C', C.c_int)]
+
+
 # every exported symbol with (restype, argtypes), in the order of include/octseg.h; tests check the library exports all of them
 _P = C.c_void_p
 LOSS_KINDS = {'dice': 0, 'bce': 1, 'dice+bce': 2}
@@ -156,6 +180,12 @@ SYMBOLS = {
     'octseg_conv_layer_slab_rows': (C.c_int, [C.c_int, C.POINTER(ConvLayerDesc), C.POINTER(C.c_int)]),
     # one launcher of the NHWC sweep kernels per call (csrc/sweep_api.cpp; wrappers in sweeps.py)
     'octseg_sweep_op': (C.c_int, [C.c_int, C.c_int, C.POINTER(_P), C.c_int, C.POINTER(C.c_longlong), C.c_int, C.POINTER(C.c_double), C.c_int, _P]),
+    # one launcher of the PAN pyramid / the MAnet position attention per call (csrc/block_api.cpp; wrappers in blockops.py)
+    'octseg_fpa_scratch_floats': (C.c_size_t, [C.c_int] * 3),
+    'octseg_fpa_gscratch_floats': (C.c_size_t, [C.c_int] * 3),
+    'octseg_fpa_uu_offset': (C.c_size_t, [C.c_int] * 3),
+    'octseg_fpa_op': (C.c_int, [C.c_int, C.c_int, C.POINTER(FpaDesc), _P]),
+    'octseg_pab_op': (C.c_int, [C.c_int, C.c_int, C.POINTER(PabDesc), _P]),
 }
 
 _lib = None

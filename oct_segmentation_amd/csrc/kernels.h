@@ -84,7 +84,7 @@ struct FpaPyrArgs {        // layers 0..5 = down1, down2, down3.1, down3.2, conv
   float* dw_[6]; float* db_[6]; float* dg_[6]; float* dbe_[6];
 };
 size_t fpa_pyr_scratch_floats(int N, int h, int w);    // forward values kept for the backward (+ the upsampled map uu [N][h][w] and 12 statistics)
-size_t fpa_pyr_gscratch_floats(int N, int h, int w);   // gradients; d(x1raw) ends at gscratch + N (h/2) (w/2)
+size_t fpa_pyr_gscratch_floats(int N, int h, int w);   // gradients; d(x1raw) is the N (h/2) (w/2) floats at gscratch + N (h/2) (w/2)
 hipError_t launch_fpa_pyr_fwd(const FpaPyrArgs& a, hipStream_t st);   // x1raw in scratch[0 .. n1) -> uu at scratch + fpa_pyr_uu_offset
 hipError_t launch_fpa_pyr_bwd(const FpaPyrArgs& a, hipStream_t st);
 static inline size_t fpa_pyr_uu_offset(int N, int h, int w) { return fpa_pyr_scratch_floats(N, h, w) - 16 - (size_t)N * h * w; }

@@ -201,7 +201,7 @@ __device__ void pyr_conv_bwd(const float* in, const float* dout, float* din, con
   __syncthreads();
 }
 // BatchNorm2d(1) + ReLU over n values: train -> batch statistics (biased variance for the normalisation, unbiased into running_var), stats[0..1] =
-// mean, rstd kept for the backward; eval -> running statistics
+// mean, rstd (the backward reads rstd and takes the mean again in double); eval -> running statistics
 __device__ void pyr_bn_relu(const float* raw, float* out, int n, const float* gamma, const float* beta, float* rmean, float* rvar, float* stats, int train,
                             double* red) {
   float mean, rstd;
@@ -228,18 +228,24 @@ __device__ void pyr_bn_relu(const float* raw, float* out, int n, const float* ga
 // gradient through ReLU + BatchNorm: dout (wrt the ReLU output; overwritten by d raw), out = the ReLU output, raw = the conv output
 __device__ void pyr_bn_relu_bwd(const float* raw, const float* out, float* dout, int n, const float* gamma, const float* stats, float* dgamma, float* dbeta,
                                 double* red) {
-  const float mean = stats[0], rstd = stats[1];
+  // The batch mean is taken again in double (the forward's order): centred on the float the forward kept in stats[0], the normalised values
+  // do not sum to zero, and on a level of a few values (rstd up to 316) the residue, times rstd^2, reaches the gradients -- the bias
+  // gradient of the conv in front, exactly zero on paper, came out at 5.7e-4 beside weight gradients near 20 (2 values, 8 x 8 map).
+  const float rstd = stats[1];
+  double sm = 0.0;
+  for (int e = threadIdx.x; e < n; e += PT) sm += (double)raw[e];
+  const double mean = pyr_block_sum(sm, red) / n;
   double s1 = 0.0, s2 = 0.0;
   for (int e = threadIdx.x; e < n; e += PT) {
     const float g = out[e] > 0.f ? dout[e] : 0.f;
-    s1 += (double)g; s2 += (double)g * ((double)(raw[e] - mean) * rstd);
+    s1 += (double)g; s2 += (double)g * (((double)raw[e] - mean) * rstd);
   }
   s1 = pyr_block_sum(s1, red); s2 = pyr_block_sum(s2, red);
   if (threadIdx.x == 0) { dbeta[0] += (float)s1; dgamma[0] += (float)s2; }
   const double c1 = s1 / n, c2 = s2 / n, A = (double)gamma[0] * rstd;
   for (int e = threadIdx.x; e < n; e += PT) {
     const float g = out[e] > 0.f ? dout[e] : 0.f;
-    dout[e] = (float)(A * ((double)g - c1 - ((double)(raw[e] - mean) * rstd) * c2));
+    dout[e] = (float)(A * ((double)g - c1 - (((double)raw[e] - mean) * rstd) * c2));
   }
   __syncthreads();
 }
@@ -347,8 +353,9 @@ __global__ __launch_bounds__(1024) void fpa_pyr_fwd_kernel(const FpaPyrArgs a) {
   __syncthreads();
   pyr_resize(tu, UU, N, h1, w1, a.h, a.w);
 }
-// Gradient scratch `g` (floats): d1 [n1] x 3 (du / dy1, dx1, dr1), d2 [n2] x 4, d3 [n3] x 3, zeroed by the launcher.  Input: a.duu [N][h][w].
-// Output: dr1 (gradient wrt x1raw, for fpa_in_bwd) in g[2 n1 ..], parameter gradients accumulated into a.dw_ / db_ / dg_ / dbe_.
+// Gradient scratch `g` (floats): d1 [n1] x 3 (du, dx1, dy1), d2 [n2] x 4 (dt, dx2, dy2, dp2), d3 [n3] x 3 (dx3, dx3a, dp3), zeroed by the launcher.
+// Input: a.duu [N][h][w].  Output: d x1raw (for fpa_in_bwd) written over dx1 in place = g[n1 .. 2 n1), as plan_backward.cpp reads it (gs + n1);
+// parameter gradients accumulated into a.dw_ / db_ / dg_ / dbe_.
 __global__ __launch_bounds__(1024) void fpa_pyr_bwd_kernel(const FpaPyrArgs a) {
   __shared__ double red[PT];
   const int N = a.N, h1 = a.h / 2, w1 = a.w / 2, h2 = h1 / 2, w2 = w1 / 2, h3 = h2 / 2, w3 = w2 / 2;

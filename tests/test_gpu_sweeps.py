@@ -13,7 +13,7 @@ parity_permute, mosaic, dw_conv, dw_wgrad (deterministic mode on and off), cam_s
 TF "same" padding on even and odd maps, deterministic mode), bnx_fwd / bnx_bwd, sefc_fwd / sefc_bwd, GroupNorm forward (gn_act_up at up 1 | 2;
 the launcher has no up = 4) and backward, dice_bwd.
 
-NOT covered (still reached only through whole networks): pan.hip's maxpool2 and fpa_*; pab.hip's pab_*.
+pan.hip's maxpool2 and fpa_* and pab.hip's pab_* have a door of their own (octseg_fpa_op / octseg_pab_op): tests/test_gpu_blockops.py.
 """
 import pytest
 import torch
