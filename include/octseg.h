@@ -552,7 +552,9 @@ int octseg_conv2d_backward_weight(int dtype, const void* x, const void* dy, floa
 typedef enum { OCTSEG_CONV_FORWARD = 0, OCTSEG_CONV_BACKWARD_DATA = 1, OCTSEG_CONV_BACKWARD_WEIGHT = 2 } octseg_conv_mode;
 /* octseg_conv_layer_route: forward / data gradient launches ...; -1 = a launch without taps (nothing runs) */
 typedef enum { OCTSEG_ROUTE_THIN = 0, OCTSEG_ROUTE_GEMM1X1, OCTSEG_ROUTE_CONV3X3P, OCTSEG_ROUTE_MFMA16, OCTSEG_ROUTE_MFMA11,
-               OCTSEG_ROUTE_MFMA_WIDEN } octseg_conv_route;
+               OCTSEG_ROUTE_MFMA_WIDEN,
+               /* octseg_tied_layer_route only: conv_mfma's masked loops over per-source tap subsets (ConvArgs::taps_per_src), by tile */
+               OCTSEG_ROUTE_MFMA11_MASKED, OCTSEG_ROUTE_MFMA16_MASKED } octseg_conv_route;
 /* ... weight gradient launches (CONVT16: the four parities of a ConvTranspose2d in one launch) */
 typedef enum { OCTSEG_WROUTE_THIN = 0, OCTSEG_WROUTE_WGRAD1X1, OCTSEG_WROUTE_CONVT16, OCTSEG_WROUTE_MFMA } octseg_wgrad_route;
 typedef struct {
@@ -576,6 +578,58 @@ int octseg_conv_layer_op(int mode, int dtype, const octseg_conv_layer_desc* desc
 /* which kernel each launch of that call runs (route_per_launch: at least 4 ints), and the slab rows of a forward; nothing is launched */
 int octseg_conv_layer_route(int mode, int dtype, const octseg_conv_layer_desc* desc, int* route_per_launch, int* nlaunch);
 int octseg_conv_layer_slab_rows(int dtype, const octseg_conv_layer_desc* desc, int* rows);
+
+/* ---- the tied decoder layer (csrc/conv_api.cpp; wrappers in convops.py) ----
+ * One call = one pass of a (nearest x2, concat, 3x3 stride 1 pad 1) decoder layer through the tied decomposition of the plan (OCTSEG_TIED, DESIGN.md
+ * section 7.7), bf16 only.  The descriptor is the one above with R = 3, stride = 1, pad = 1: src[0] the `up` source (Ca channels, stored
+ * at H / 2 x W / 2), src[1..] the skip sources at full resolution (Cs channels together; none: Cs = 0); wscale, bias, relu_out, the slab and
+ * head stay unset.  The weight images (4x4 image of sums of 3x3 taps over the Ca slice, forward and data gradient; the 3x3 image of the skip
+ * slice) are packed into `scratch` by launch_pack_all with the plan's pack jobs; scratch >= octseg_tied_layer_scratch_bytes().
+ *   FORWARD          what tied_forward() runs without its statistics sweep: the skip slice's 3x3 stores dst[0] = T[N][H][W][Cout] (rule 'staged'),
+ *                    the four parity launches of the 4x4 stride-2 kernel add to it, each T(f32(T(partial)) + old); Cs = 0: each stores its pixels
+ *   BACKWARD_DATA    dst[0] = T[N][H / 2][W / 2][Ca]: T(y), or T(f32(T(y)) + old) with accum, y = the WHOLE sum of the low-resolution gradient
+ *                    (one masked launch over dy's four parity planes, or the 16-tap stride-2 launch): nothing is pooled, dst[0].pool = 0;
+ *                    dst[i] = T[N][H][W][C_i] (+ accum) of the skip sources from the skip slice's 3x3 data gradient
+ *   BACKWARD_WEIGHT  dW f[3][3][Cout][Cin] += the fold of the 4x4 image's gradient (wgrad_convt16 or four parity launches) and the skip slice's;
+ *                    wg_target = split-K width (0: the full width; octseg_side_wgs(): the plan's narrowing on its side stream)
+ * Refused before any launch: what octseg_conv_layer_op refuses in pointers and fused fields, a set wscale / relu_out / slab / head / pool,
+ * accum on a forward, a scratch too small, wg_target < 0: OCTSEG_BAD_ARG; a layer the plan would not tie (tie_eligible: Ca >= 64, Cs = 0 or
+ * >= 32, Cout >= 32, all in whole vectors, only src[0] upsampled, no bias): OCTSEG_BAD_SHAPE; f32 and f16: OCTSEG_BAD_DTYPE.
+ * FORWARD and BACKWARD_DATA upload the four-entry job table and wait for that copy on `stream` before they enqueue the launches. */
+int octseg_tied_layer_op(int pass, int dtype, const octseg_conv_layer_desc* desc, int wg_target, void* stream);
+/* route_per_launch: at least 6 ints, in launch order (forward: skip, four parities; data gradient: the up slice's launch, skip; weight gradient:
+ * CONVT16 or four parities, skip; the pack, clear and fold launches are not listed) */
+int octseg_tied_layer_route(int pass, int dtype, const octseg_conv_layer_desc* desc, int wg_target, int* route_per_launch, int* nlaunch);
+size_t octseg_tied_layer_scratch_bytes(int dtype, const octseg_conv_layer_desc* desc);   /* 0: refused (octseg_last_error says why) */
+int octseg_side_wgs(void);
+
+/* ---- single-launch door to the stem kernels (csrc/stem_api.cpp; wrappers in convops.py) ----
+ * One call = one launch over the NCHW f32 frame img f[N][3][H][W], normalised on the fly when normalize = 1: every kernel sees the frame as
+ * T(f32(f32(raw - mean[c]) * f32(1 / stdv[c]))), zero outside (the padding is applied AFTER the normalisation).  OH x OW = H / 2 x W / 2.
+ *   IM2COL   launch_stem_im2col: col T[N][OH][OW][KP], column k = (r * ksize + s) * 3 + c holds pixel (2 oy - pad + r, 2 ox - pad + s) of channel
+ *            c, columns >= 3 ksize^2 are zero.  (ksize, pad, KP) = (7, 3, 160) ResNet, (3, 1, 32) RegNet, (3, 0, 32) EfficientNet; every dtype.
+ *            The f32 and deterministic paths run the stem as this launch + a 1x1 layer of KP input channels (octseg_conv_layer_op).
+ *   FORWARD  thin.hip's 7x7 stride-2 pad-3 conv 3 -> 64 straight from the frame (bf16, f16): w f[64][160] with k as above (columns >= 147 are
+ *            never read); y T[N][OH][OW][64] = T(conv (+ bias, relu_out)); training: stat_slab f[slab_row0 + rows][64][2] = per row (sum y,
+ *            sum y^2) of the f32 y, rows = octseg_stem_slab_rows() (one per workgroup); eval: wscale f[64] (W * wscale in f32, then rounded to
+ *            T), bias f[64], relu_out (needs bias, excludes stat_slab)
+ *   WGRAD    thin.hip's weight gradient (bf16, not in deterministic mode): dy T[N][OH][OW][64]; dW f[64][160] ACCUMULATED with atomics onto
+ *            what is there; columns 147..159 receive +0
+ * Refused before any launch: a null required or misaligned (16 B) pointer, relu_out without bias or with stat_slab, a negative slab_row0,
+ * weight-gradient fields in a forward and the reverse, normalize with a non-positive std, WGRAD in deterministic mode: OCTSEG_BAD_ARG;
+ * odd or empty H / W, another (ksize, pad, KP), 2^31 elements or more: OCTSEG_BAD_SHAPE; f32 in FORWARD / WGRAD, f16 in WGRAD: OCTSEG_BAD_DTYPE. */
+typedef enum { OCTSEG_STEM_IM2COL = 0, OCTSEG_STEM_FORWARD = 1, OCTSEG_STEM_WGRAD = 2 } octseg_stem_stage;
+typedef struct {
+  int N, H, W;
+  const float* img;
+  int normalize; float mean[3], stdv[3];
+  int ksize, pad, KP; void* col;                        /* IM2COL */
+  const float* w; const float* wscale; const float* bias; int relu_out;
+  void* y; float* stat_slab; int slab_row0;             /* FORWARD */
+  const void* dy; float* dW;                            /* WGRAD */
+} octseg_stem_desc;
+int octseg_stem_op(int stage, int dtype, const octseg_stem_desc* desc, void* stream);
+int octseg_stem_slab_rows(int N, int H, int W);         /* thin_stem_rows: slab rows a FORWARD writes (0: empty frame) */
 
 /* ---- single-op door to the NHWC sweep kernels (BatchNorm finalize / apply / backward, pools, resamplers, gates, gradient plumbing) ----
  * One call = one launcher of csrc/kernels.h on `stream` (bn_bwd_finalize etc. included: the caller chains reduce -> finalize -> apply).

@@ -67,6 +67,13 @@ class ConvLayerDesc(C.Structure):   # octseg_conv_layer_desc
                 ('scratch_bytes', C.c_size_t)]
 
 
+class StemDesc(C.Structure):   # octseg_stem_desc
+    _fields_ = [('N', C.c_int), ('H', C.c_int), ('W', C.c_int), ('img', C.c_void_p), ('normalize', C.c_int), ('mean', C.c_float * 3),
+                ('stdv', C.c_float * 3), ('ksize', C.c_int), ('pad', C.c_int), ('KP', C.c_int), ('col', C.c_void_p), ('w', C.c_void_p),
+                ('wscale', C.c_void_p), ('bias', C.c_void_p), ('relu_out', C.c_int), ('y', C.c_void_p), ('stat_slab', C.c_void_p),
+                ('slab_row0', C.c_int), ('dy', C.c_void_p), ('dW', C.c_void_p)]
+
+
 _PF6 = C.c_void_p * 6
 
 
@@ -178,6 +185,14 @@ SYMBOLS = {
     'octseg_conv_layer_op': (C.c_int, [C.c_int, C.c_int, C.POINTER(ConvLayerDesc), _P]),
     'octseg_conv_layer_route': (C.c_int, [C.c_int, C.c_int, C.POINTER(ConvLayerDesc), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     'octseg_conv_layer_slab_rows': (C.c_int, [C.c_int, C.POINTER(ConvLayerDesc), C.POINTER(C.c_int)]),
+    # one pass of a tied decoder layer per call, with the plan's images and launches (csrc/conv_api.cpp; wrappers in convops.py)
+    'octseg_tied_layer_op': (C.c_int, [C.c_int, C.c_int, C.POINTER(ConvLayerDesc), C.c_int, _P]),
+    'octseg_tied_layer_route': (C.c_int, [C.c_int, C.c_int, C.POINTER(ConvLayerDesc), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    'octseg_tied_layer_scratch_bytes': (C.c_size_t, [C.c_int, C.POINTER(ConvLayerDesc)]),
+    'octseg_side_wgs': (C.c_int, []),
+    # one stem launch per call: im2col rows, thin.hip's 7x7 forward and weight gradient (csrc/stem_api.cpp; wrappers in convops.py)
+    'octseg_stem_op': (C.c_int, [C.c_int, C.c_int, C.POINTER(StemDesc), _P]),
+    'octseg_stem_slab_rows': (C.c_int, [C.c_int] * 3),
     # one launcher of the NHWC sweep kernels per call (csrc/sweep_api.cpp; wrappers in sweeps.py)
     'octseg_sweep_op': (C.c_int, [C.c_int, C.c_int, C.POINTER(_P), C.c_int, C.POINTER(C.c_longlong), C.c_int, C.POINTER(C.c_double), C.c_int, _P]),
     # one launcher of the PAN pyramid / the MAnet position attention per call (csrc/block_api.cpp; wrappers in blockops.py)

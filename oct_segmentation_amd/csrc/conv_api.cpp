@@ -4,6 +4,7 @@
 // builds for one layer pass (plan_forward.cpp OP_CONV, plan_backward.cpp conv_backward) from a plain C descriptor and hands them to
 // launch_conv / launch_wgrad: the kernels and their routing stay what they are.  It refuses, before any launch, what the launchers cannot
 // take.  Buffer sizes are the caller's contract (oct_segmentation_amd/convops.py checks them): see include/octseg.h.
+// octseg_tied_layer_op (second half of this file) is the same door for the tied decomposition of a decoder layer.
 #include "plan_internal.h"
 
 using namespace octseg;
@@ -215,5 +216,267 @@ int octseg_conv_layer_slab_rows(int dtype, const octseg_conv_layer_desc* d, int*
   *rows = B.rows;
   return OCTSEG_OK;
 }
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------- the tied decoder layer
+// octseg_tied_layer_op: one pass of a (nearest x2, concat, 3x3) decoder layer through the tied decomposition (ConvLayer::tie), built from the
+// same descriptor as above exactly as tied_forward (plan_forward.cpp) and the `L.tie & 2` / `L.tie & 4` branches of conv_backward
+// (plan_backward.cpp) build it: eligibility, image geometry and pack jobs come from the helpers the plan builder calls (plan_geom.cpp).
+namespace {
+
+constexpr size_t TIE_TAB_BYTES = 512, TIE_PREFIX_BYTES = 512;   // job table (4 PackJobs) and prefix sums at the head of the caller's scratch
+static_assert(4 * sizeof(PackJob) <= TIE_TAB_BYTES, "the job table fits its slot");
+
+struct Tied {
+  int Ca = 0, Cs = 0, ns = 0;
+  Geom gu{}, gs{};
+  TieImages im{};
+  TieOffsets at{};
+  size_t dk4_off = 0, bytes = 0;          // the weight gradient's f32 scratch ([16][O][Ca] + [9][O][Cs]) and the whole scratch
+  std::vector<PackJob> jobs; std::vector<unsigned long long> prefix; unsigned long long total = 0;
+  std::vector<ConvArgs> conv;             // forward: (skip,) four parities; data gradient: the up slice's launch(es) (, skip)
+  std::vector<WgradArgs> wg;              // weight gradient: the four parity launches (, skip)
+  bool convt16 = false, masked = false;
+};
+
+// layer geometry only (what octseg_tied_layer_scratch_bytes needs); pointers are looked at by tied_build
+int tied_shape(int dtype, const octseg_conv_layer_desc* d, Tied& B) {
+  const std::string who = "tied_layer_op: ";
+  auto bad_shape = [&](const char* m) { return fail(OCTSEG_BAD_SHAPE, who + m); };
+  if (dtype != OCTSEG_F32 && dtype != OCTSEG_BF16 && dtype != OCTSEG_F16) return fail(OCTSEG_BAD_DTYPE, who + "dtype must be f32, bf16 or f16");
+  if (dtype != OCTSEG_BF16) return fail(OCTSEG_BAD_DTYPE, who + "the tied decomposition is a bf16 training path");
+  if (d == nullptr) return fail(OCTSEG_BAD_ARG, who + "null descriptor");
+  if (d->N < 1 || d->H < 1 || d->W < 1 || d->Cin < 1 || d->Cout < 1) return bad_shape("empty tensor");
+  if (d->nsrc < 1 || d->nsrc > MAX_SRC) return bad_shape("1 .. 5 sources");
+  if ((long long)d->N * d->H * d->W * std::max(d->Cin, d->Cout) >= (1ll << 31)) return bad_shape("tensor of 2^31 elements or more");
+  int c = 0;
+  TieQuery q{};
+  q.esz = (int)dtype_size(dtype); q.transposed = d->transposed != 0; q.head = d->head != 0; q.has_bn = true; q.has_bias = d->bias != nullptr;
+  q.R = q.S = d->R; q.stride = d->stride; q.pad = d->pad; q.nsrc = d->nsrc;
+  q.up0_whole_grad = d->src[0].up == 1; q.skips_plain_grad = true;
+  for (int i = 0; i < d->nsrc; ++i) {
+    const octseg_conv_src& s = d->src[i];
+    if (s.C < 1 || s.C % 8 != 0) return bad_shape("a source's C is not a whole number of 16-byte vectors");
+    if (s.up != 0 && s.up != 1) return fail(OCTSEG_BAD_ARG, who + "up is 0 or 1");
+    if ((s.H << s.up) != d->H || (s.W << s.up) != d->W) return bad_shape("a source's stored extent is not H >> up x W >> up");
+    if (i > 0 && s.up) q.skips_plain_grad = false;
+    c += s.C;
+  }
+  if (c != d->Cin) return bad_shape("the sources' channels do not add up to Cin");
+  q.Ca = d->src[0].C; q.Cs = d->Cin - q.Ca; q.Cout = d->Cout;
+  if (d->Cout % 8 != 0) return bad_shape("Cout is not a whole number of 16-byte vectors");
+  if (!tie_eligible(q)) return bad_shape("the plan would not tie this layer (tie_eligible: src[0] nearest x2 with >= 64 channels, plain skips of 0 or >= 32, 3x3 stride 1 pad 1, Cout >= 32)");
+  B.Ca = q.Ca; B.Cs = q.Cs; B.ns = d->nsrc;
+  B.gu = Geom{4, 4, 2, 1, true, d->N, d->H / 2, d->W / 2, B.Ca, d->H, d->W, d->Cout};   // (= tie_geom_up / tie_geom_skip of the plan's layer)
+  B.gs = Geom{3, 3, 1, 1, false, d->N, d->H, d->W, B.Cs, d->H, d->W, d->Cout};
+  B.im = tie_images(dtype, B.gu, B.gs);
+  size_t off = TIE_TAB_BYTES + TIE_PREFIX_BYTES;
+  B.at.fu = off; off += align_up(conv_image_bytes(B.im.pk_fu, 16));
+  B.at.du = off; off += align_up(conv_image_bytes(B.im.pk_du, B.im.du_taps()));
+  if (B.Cs > 0) {
+    B.at.fs = off; off += align_up(conv_image_bytes(B.im.pk_fs, 9));
+    B.at.ds = off; off += align_up(conv_image_bytes(B.im.pk_ds, 9));
+  }
+  B.dk4_off = off; off += align_up(((size_t)16 * B.Ca + (size_t)9 * B.Cs) * d->Cout * sizeof(float));
+  B.bytes = off;
+  tie_pack_jobs(B.im, B.at, 0, d->Cout, d->Cin, B.Ca, B.Cs, B.jobs, B.prefix, B.total);
+  return OCTSEG_OK;
+}
+
+int tied_build(int pass, int dtype, const octseg_conv_layer_desc* d, int wg_target, Tied& B) {
+  const std::string who = "tied_layer_op: ";
+  auto bad_arg = [&](const char* m) { return fail(OCTSEG_BAD_ARG, who + m); };
+  if (pass != OCTSEG_CONV_FORWARD && pass != OCTSEG_CONV_BACKWARD_DATA && pass != OCTSEG_CONV_BACKWARD_WEIGHT) return bad_arg("unknown pass");
+  const int rc = tied_shape(dtype, d, B);
+  if (rc != OCTSEG_OK) return rc;
+  const bool fwd = pass == OCTSEG_CONV_FORWARD, dgrad = pass == OCTSEG_CONV_BACKWARD_DATA;
+  if (wg_target < 0) return bad_arg("negative wg_target");
+  if (d->wscale || d->bias || d->relu_out || d->stat_slab || d->slab_row0 || d->head)
+    return bad_arg("wscale, bias, relu_out, the slab and head mode are not part of a tied pass (training only; the statistics are a sweep of their own)");
+  if (!aligned(d->w) || !aligned(d->dy) || !aligned(d->dW) || !aligned(d->scratch)) return bad_arg("misaligned pointer");
+  if (d->scratch == nullptr) return bad_arg("null scratch");
+  if (d->scratch_bytes < B.bytes) return bad_arg("scratch smaller than octseg_tied_layer_scratch_bytes()");
+  SrcDesc src[MAX_SRC];
+  int c0 = 0;
+  for (int i = 0; i < d->nsrc; ++i) {
+    const octseg_conv_src& s = d->src[i];
+    // (the data gradient reads dy: its sources only say where the gradient goes, their affine fields are not looked at)
+    if (!dgrad && (s.scale != nullptr) != (s.shift != nullptr)) return bad_arg("scale and shift come together");
+    if (!dgrad && s.relu && s.scale == nullptr) return bad_arg("relu without the affine (the plan never builds it)");
+    if (!dgrad && (s.ptr == nullptr || !aligned(s.ptr) || !aligned(s.scale) || !aligned(s.shift))) return bad_arg("null or misaligned source pointer");
+    SrcDesc o;
+    o.ptr = s.ptr; o.scale = dgrad ? nullptr : s.scale; o.shift = dgrad ? nullptr : s.shift; o.C = s.C; o.c0 = c0; o.H = s.H; o.W = s.W; o.up = s.up;
+    o.relu = s.relu ? 1 : 0;
+    src[i] = o;
+    c0 += s.C;
+  }
+  char* ws = (char*)d->scratch;
+  const int O = d->Cout;
+  if (fwd) {   // tied_forward
+    if (d->w == nullptr) return bad_arg("null weight");
+    if (d->dst[0].ptr == nullptr || !aligned(d->dst[0].ptr)) return bad_arg("null or misaligned destination");
+    if (d->dst[0].accum || d->dst[0].pool) return bad_arg("the tied forward stores its output (no accum, no pool)");
+    DstDesc dd;
+    dd.ptr = d->dst[0].ptr; dd.C = O; dd.c0 = 0; dd.cn = O; dd.H = d->H; dd.W = d->W; dd.accum = 0; dd.pool = 0;
+    if (B.Cs > 0) {
+      std::vector<ConvArgs> v;
+      fwd_launches(B.gs, v);
+      ConvArgs& a = v[0];
+      a.nsrc = B.ns - 1;
+      for (int i = 1; i < B.ns; ++i) { a.src[i - 1] = src[i]; a.src[i - 1].c0 -= B.Ca; }
+      a.W = ws + B.at.fs;
+      a.dst[0] = dd; a.ndst = 1; a.out_mode = OUT_STORE;
+      B.conv.push_back(a);
+    }
+    std::vector<ConvArgs> v;
+    fwd_launches(B.gu, v);
+    for (auto& a : v) {
+      a.nsrc = 1; a.src[0] = src[0]; a.src[0].up = 0; a.src[0].c0 = 0;
+      a.W = ws + B.at.fu;
+      dd.accum = B.Cs > 0 ? 1 : 0;   // (the four parities are disjoint: without a skip launch each one stores its own pixels)
+      a.dst[0] = dd; a.ndst = 1; a.out_mode = OUT_STORE;
+      B.conv.push_back(a);
+    }
+  } else if (dgrad) {   // conv_backward, L.tie & 2
+    if (d->w == nullptr || d->dy == nullptr) return bad_arg("null weight or dy");
+    for (int i = 0; i < d->nsrc; ++i) {
+      if (d->dst[i].ptr == nullptr || !aligned(d->dst[i].ptr)) return bad_arg("null or misaligned destination");
+      if (d->dst[i].pool) return bad_arg("pool: the tied data gradient is computed at the low resolution, nothing is pooled");
+    }
+    const size_t esz = dtype_size(dtype);
+    std::vector<ConvArgs> lu;
+    B.masked = B.im.du_masked;
+    if (B.masked) { lu.resize(1); tied_dgrad_masked(B.gu, lu[0]); }
+    else dgrad_launches(B.gu, lu);   // (one launch: 16 taps at stride 2 over dy)
+    for (int k = 0; k < (int)lu.size(); ++k) {
+      ConvArgs& a = lu[k];
+      if (B.masked) {
+        for (int p = 0; p < 4; ++p) {   // plane p of dy as a tensor of its own: first pixel (p >> 1, p & 1), doubled pixel and row strides
+          SrcDesc& s = a.src[p];
+          s.ptr = (const char*)d->dy + ((size_t)(p >> 1) * d->W + (p & 1)) * O * esz;
+          s.scale = nullptr; s.shift = nullptr; s.C = 2 * O; s.c0 = p * O; s.H = d->H / 2; s.W = d->W; s.up = 0; s.relu = 0;
+        }
+      } else {
+        SrcDesc s;
+        s.ptr = d->dy; s.scale = nullptr; s.shift = nullptr; s.C = O; s.c0 = 0; s.H = d->H; s.W = d->W; s.up = 0; s.relu = 0;
+        a.src[0] = s; a.nsrc = 1;
+        a.Cin = O;
+      }
+      a.W = ws + B.at.du;
+      DstDesc t;
+      t.ptr = d->dst[0].ptr; t.C = B.Ca; t.c0 = 0; t.cn = B.Ca; t.H = d->H / 2; t.W = d->W / 2; t.accum = k == 0 ? (d->dst[0].accum ? 1 : 0) : 1; t.pool = 0;
+      a.dst[0] = t; a.ndst = 1; a.out_mode = OUT_STORE; a.bias = nullptr; a.stat_slab = nullptr;
+      B.conv.push_back(a);
+    }
+    if (B.Cs > 0) {
+      std::vector<ConvArgs> ls;
+      dgrad_launches(B.gs, ls);
+      ConvArgs& a = ls[0];
+      SrcDesc s;
+      s.ptr = d->dy; s.scale = nullptr; s.shift = nullptr; s.C = O; s.c0 = 0; s.H = d->H; s.W = d->W; s.up = 0; s.relu = 0;
+      a.src[0] = s; a.nsrc = 1;
+      a.Cin = O;
+      a.W = ws + B.at.ds;
+      int nd = 0, cc = 0;
+      for (int i = 1; i < d->nsrc; ++i) {
+        DstDesc t;
+        t.ptr = d->dst[i].ptr; t.C = src[i].C; t.c0 = cc; t.cn = src[i].C; t.H = d->H; t.W = d->W; t.accum = d->dst[i].accum ? 1 : 0; t.pool = 0;
+        a.dst[nd++] = t;
+        cc += src[i].C;
+      }
+      a.ndst = nd; a.out_mode = OUT_STORE; a.bias = nullptr; a.stat_slab = nullptr;
+      B.conv.push_back(a);
+    }
+  } else {   // conv_backward, L.tie & 4
+    if (d->dy == nullptr || d->dW == nullptr) return bad_arg("null dy or dW");
+    float* dK4 = (float*)(ws + B.dk4_off);
+    float* dW3s = dK4 + (size_t)16 * O * B.Ca;
+    wgrad_launches(B.gu, B.wg);
+    for (auto& a : B.wg) {
+      a.nsrc = 1; a.src[0] = src[0]; a.src[0].up = 0; a.src[0].c0 = 0;
+      a.dy = d->dy; a.dyC = O; a.dW = dK4; a.stamp = nullptr;
+      a.wg_target = wg_target;
+    }
+    B.convt16 = wgrad_convt16_eligible(B.wg[0], dtype);   // all four parities from one staged window (wgrad_convt.hip)
+    if (B.Cs > 0) {
+      std::vector<WgradArgs> lw;
+      wgrad_launches(B.gs, lw);
+      WgradArgs& a = lw[0];
+      a.nsrc = B.ns - 1;
+      for (int i = 1; i < B.ns; ++i) { a.src[i - 1] = src[i]; a.src[i - 1].c0 -= B.Ca; }
+      a.dy = d->dy; a.dyC = O; a.dW = dW3s; a.stamp = nullptr;
+      a.wg_target = wg_target;
+      B.wg.push_back(a);
+    }
+  }
+  return OCTSEG_OK;
+}
+
+int tied_route_of(const ConvArgs& a, int dtype) {
+  const int r = public_route(a, dtype);
+  if (a.taps_per_src == 0) return r;
+  return r == OCTSEG_ROUTE_MFMA11 ? OCTSEG_ROUTE_MFMA11_MASKED : r == OCTSEG_ROUTE_MFMA16 ? OCTSEG_ROUTE_MFMA16_MASKED : r;
+}
+
+}  // namespace
+
+extern "C" {
+
+int octseg_tied_layer_op(int pass, int dtype, const octseg_conv_layer_desc* d, int wg_target, void* stream) {
+  Tied B;
+  const int rc = tied_build(pass, dtype, d, wg_target, B);
+  if (rc != OCTSEG_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  char* ws = (char*)d->scratch;
+  if (pass == OCTSEG_CONV_BACKWARD_WEIGHT) {
+    const size_t O = d->Cout;
+    float* dK4 = (float*)(ws + B.dk4_off);
+    float* dW3s = dK4 + (size_t)16 * O * B.Ca;
+    HIPCHK(hipMemsetAsync(dK4, 0, ((size_t)16 * B.Ca + (size_t)9 * B.Cs) * O * sizeof(float), st));
+    if (B.convt16) HIPCHK(launch_wgrad_convt16(dtype, B.wg[0], st));
+    else
+      for (int k = 0; k < 4; ++k) HIPCHK(launch_wgrad(dtype, B.wg[k], st));
+    if (B.Cs > 0) HIPCHK(launch_wgrad(dtype, B.wg[4], st));
+    HIPCHK(launch_tied_fold(dK4, B.Cs > 0 ? dW3s : nullptr, d->dW, d->Cout, B.Ca, B.Cs, st));
+    return OCTSEG_OK;
+  }
+  // the images as the plan packs them: one launch_pack_all over the layer's jobs (table and prefix sums at the head of the scratch)
+  HIPCHK(hipMemcpyAsync(ws, B.jobs.data(), B.jobs.size() * sizeof(PackJob), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(ws + TIE_TAB_BYTES, B.prefix.data(), B.prefix.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));   // (the two host vectors die with this call)
+  HIPCHK(launch_pack_all(dtype, d->w, ws, (const PackJob*)ws, (const unsigned long long*)(ws + TIE_TAB_BYTES), (int)B.jobs.size(), B.total, 0, st));
+  for (auto& a : B.conv) HIPCHK(launch_conv(dtype, a, st));
+  return OCTSEG_OK;
+}
+
+int octseg_tied_layer_route(int pass, int dtype, const octseg_conv_layer_desc* d, int wg_target, int* route_per_launch, int* nlaunch) {
+  if (route_per_launch == nullptr || nlaunch == nullptr) return fail(OCTSEG_BAD_ARG, "tied_layer_route: null output");
+  Tied B;
+  const int rc = tied_build(pass, dtype, d, wg_target, B);
+  if (rc != OCTSEG_OK) return rc;
+  int n = 0;
+  if (pass == OCTSEG_CONV_BACKWARD_WEIGHT) {
+    auto name = [&](const WgradArgs& a) {
+      const WgradRoute r = wgrad_route(a, dtype);
+      return a.ntaps <= 0 ? -1 : r == WROUTE_THIN ? (int)OCTSEG_WROUTE_THIN : r == WROUTE_1X1 ? (int)OCTSEG_WROUTE_WGRAD1X1 : (int)OCTSEG_WROUTE_MFMA;
+    };
+    if (B.convt16) route_per_launch[n++] = OCTSEG_WROUTE_CONVT16;
+    else
+      for (int k = 0; k < 4; ++k) route_per_launch[n++] = name(B.wg[k]);
+    if (B.Cs > 0) route_per_launch[n++] = name(B.wg[4]);
+  } else {
+    for (auto& a : B.conv) route_per_launch[n++] = tied_route_of(a, dtype);
+  }
+  *nlaunch = n;
+  return OCTSEG_OK;
+}
+
+size_t octseg_tied_layer_scratch_bytes(int dtype, const octseg_conv_layer_desc* d) {
+  Tied B;
+  return tied_shape(dtype, d, B) == OCTSEG_OK ? B.bytes : 0;
+}
+
+int octseg_side_wgs(void) { return side_wgs(); }
 
 }  // extern "C"

@@ -837,8 +837,13 @@ __global__ __launch_bounds__(256) void stem_im2col_kernel(const float* img, void
         const int tap = k / 3, ci = k - tap * 3;
         const int r = tap / KS, s = tap - r * KS;
         const int iy = 2 * oy - PT + r, ix = 2 * ox - PT + s;     // (PT: 3 ResNet, 1 RegNet, 0 EfficientNet's static 'same' padding)
-        if (iy >= 0 && iy < H && ix >= 0 && ix < W)
+        if (iy >= 0 && iy < H && ix >= 0 && ix < W) {
           val = (img[(((size_t)n * 3 + ci) * H + iy) * W + ix] - mean[ci]) * inv[ci];
+          // the product is an f32 BEFORE it is rounded to T, as in thin.hip's stem (whose frame window waits in f32 registers): left to
+          // itself the f16 instantiation folds multiply and conversion into one v_fma_mixlo_f16, which rounds the exact product once --
+          // another f16 than the two-step value on about one element in two thousand (tests/test_gpu_stemops.py, k3p1_norm f16)
+          asm volatile("" : "+v"(val));
+        }
       }
       x[i] = val;
     }

@@ -28,6 +28,14 @@ int conv_mfma_tile(const ConvArgs& a, int dtype);
 //   thin.hip (the accumulators go to memory straight from registers):
 //     store  T(y);   accum  T(y + old);           pool  T(old + (y00 + y10 + y01 + y11)), nothing rounded before the last step.
 // BatchNorm statistics are always those of the f32 `y`, over the pixels inside the map.  tests/conv_ref.py states both rules.
+// The tied decoder layer (ConvLayer::tie; its launches all run in conv_mfma_kernel) follows from the first rule, launch by launch:
+//   forward        the skip slice's launch stores T(s), the parity launch that owns a pixel adds its T(u):  y = T(f32(T(u)) + T(s));
+//                  without skip channels each parity launch stores T(u).  (u, s: the sums over the up / skip channels.)
+//   data gradient  of the `up` source, at the LOW resolution:  T(g);  accum  T(f32(T(g)) + old),  g = the whole sum over the 2x2 quad and all its
+//                  taps in one f32 accumulator -- the pooled rule above (four T(q) added to old) does not apply: nothing is pooled
+//   weight gradient  f32 throughout: dW3 += fold(dK4) (+ dW3s), launch_tied_fold.     tests/tied_cases.py states these rules.
+// The stem kernels see the frame as T(f32(f32(raw - mean) * f32(1 / std))), zero outside the frame (tests/stem_ref.py): thin.hip keeps the f32 product
+// in registers, stem_im2col_kernel must not let the f16 conversion absorb the multiply (v_fma_mixlo_f16 rounds the exact product once).
 bool conv_masked_eligible(const ConvArgs& a, int dtype);   // launches with per-source tap subsets (ConvArgs::taps_per_src): can the masked loop take this one?
 
 // gemm1x1.hip: stride-1, single-source 1x1 convs and their data gradients as a persistent GEMM (2-byte dtypes); consumes the same

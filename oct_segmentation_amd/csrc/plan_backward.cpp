@@ -10,7 +10,7 @@ namespace detail {
 // chain nothing to start on until its workgroups retire; on 144-160 CUs it takes 30 % longer by itself (24.5 against 18.9 ms per step at 160, alone)
 // and the step gets shorter: 65.1 -> 63.0 ms at 144 workgroups (ABAB on one box; 112: 67.8, 128: 63.5, 136: 63.0, 152: 63.3, 160: 63.4-63.7, 176: 63.7).  On the caller's own stream (one-stream
 // mode, the kernels-alone pass of bench.py) nothing runs beside it and it keeps the full width (wg_target = 0).
-static int side_wgs() { return 144; }
+int side_wgs() { return 144; }
 
 // BN backward of BN `bn` over raw tensor y: g -> dy (written to grad(y))
 static int bn_backward(Exec& E, int bn, const void* g, int mask, const void* out_mask, void* res_grad = nullptr, int res_store = 0,

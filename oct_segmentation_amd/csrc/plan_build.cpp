@@ -957,37 +957,25 @@ int build_plan(octseg_plan* P) {
       L.wimg_dgrad_off = off; off += align_up(conv_image_bytes(L.pk_dgrad, wtaps));
     }
     L.tie = 0;
-    if (tie_mask() != 0 && esz == 2 && !L.transposed && !L.stem && !L.head && !L.sliced && !L.accum_out && L.R == 3 && L.S == 3 && L.stride == 1 &&
-        L.pad == 1 && L.bn >= 0 && L.b < 0 && !L.srcs.empty() && L.srcs[0].up && L.srcs[0].cn == 0 && P->tensors[L.srcs[0].v.t].need_grad) {
-      bool ok = true;
-      for (size_t i = 1; i < L.srcs.size(); ++i) ok = ok && !L.srcs[i].up && L.srcs[i].cn == 0 && P->tensors[L.srcs[i].v.t].need_grad;
-      const int Ca = P->tensors[L.srcs[0].v.t].C, Cs = L.Cin - Ca;
-      // (narrow layers stay whole: below 64 channels a launch is a single K chunk and the thin kernels own the 16 / 32-channel decoder tail)
-      if (ok && Ca >= 64 && Ca % 8 == 0 && Cs % 8 == 0 && L.Cout >= 32 && (Cs == 0 || Cs >= 32)) {
+    if (tie_mask() != 0 && !L.srcs.empty()) {
+      TieQuery q{};
+      q.esz = (int)esz; q.transposed = L.transposed; q.stem = L.stem; q.head = L.head; q.sliced = L.sliced; q.accum_out = L.accum_out;
+      q.has_bn = L.bn >= 0; q.has_bias = L.b >= 0; q.R = L.R; q.S = L.S; q.stride = L.stride; q.pad = L.pad; q.nsrc = (int)L.srcs.size();
+      q.up0_whole_grad = L.srcs[0].up && L.srcs[0].cn == 0 && P->tensors[L.srcs[0].v.t].need_grad;
+      q.skips_plain_grad = true;
+      for (size_t i = 1; i < L.srcs.size(); ++i)
+        q.skips_plain_grad = q.skips_plain_grad && !L.srcs[i].up && L.srcs[i].cn == 0 && P->tensors[L.srcs[i].v.t].need_grad;
+      q.Ca = P->tensors[L.srcs[0].v.t].C; q.Cs = L.Cin - q.Ca; q.Cout = L.Cout;
+      if (tie_eligible(q)) {
+        const int Ca = q.Ca, Cs = q.Cs;
         L.tie = tie_mask(); L.tie_Ca = Ca; L.tie_Cs = Cs;
-        const Geom gu{4, 4, 2, 1, true, L.N, L.IH / 2, L.IW / 2, Ca, L.OH, L.OW, L.Cout};
-        const Geom gs{3, 3, 1, 1, false, L.N, L.IH, L.IW, Cs, L.OH, L.OW, L.Cout};
-        std::vector<ConvArgs> v;
-        fwd_launches(gu, v);
-        L.tie_pk_fu = conv_pack_info(v[0], P->dtype);
+        const TieImages im = tie_images(P->dtype, tie_geom_up(L), tie_geom_skip(L));
+        L.tie_pk_fu = im.pk_fu; L.tie_pk_du = im.pk_du; L.tie_du_masked = im.du_masked;
         L.tie_fu_off = off; off += align_up(conv_image_bytes(L.tie_pk_fu, 16));
-        v.clear();
-        L.tie_du_masked = false;
-        if (L.Cout % 64 == 0) {   // one masked launch over the four parity planes: the planes are whole K chunks
-          ConvArgs am;
-          tied_dgrad_masked(gu, am);
-          DstDesc dd{}; dd.H = gu.IH; dd.W = gu.IW; dd.C = Ca; dd.cn = Ca; am.dst[0] = dd; am.ndst = 1;
-          if (conv_masked_eligible(am, P->dtype)) { L.tie_du_masked = true; v.push_back(am); }
-        }
-        if (!L.tie_du_masked) dgrad_launches(gu, v);
-        L.tie_pk_du = conv_pack_info(v[0], P->dtype);
-        L.tie_du_off = off; off += align_up(conv_image_bytes(L.tie_pk_du, L.tie_du_masked ? 9 : 16));
+        L.tie_du_off = off; off += align_up(conv_image_bytes(L.tie_pk_du, im.du_taps()));
         if (Cs > 0) {
-          v.clear(); fwd_launches(gs, v);
-          L.tie_pk_fs = conv_pack_info(v[0], P->dtype);
+          L.tie_pk_fs = im.pk_fs; L.tie_pk_ds = im.pk_ds;
           L.tie_fs_off = off; off += align_up(conv_image_bytes(L.tie_pk_fs, 9));
-          v.clear(); dgrad_launches(gs, v);
-          L.tie_pk_ds = conv_pack_info(v[0], P->dtype);
           L.tie_ds_off = off; off += align_up(conv_image_bytes(L.tie_pk_ds, 9));
         }
         tie_scratch = std::max(tie_scratch, ((size_t)16 * Ca + (size_t)9 * Cs) * L.Cout * sizeof(float));
@@ -1039,20 +1027,10 @@ int build_plan(octseg_plan* P) {
       P->pack_jobs.push_back(j);
       P->pack_total += (unsigned long long)taps * pk.nchunks * pk.ntiles * pk.BN * (pk.RB / 16);
     }
-    if (L.tie) {   // the tied images: 4x4 kernel over the upsampled source's channels, the plain 3x3 over the skip channels (training only: no fold)
-      auto add = [&](size_t dst, int ntaps, int I, int c0, int tr, int tied, const ConvPackInfo& pk) {
-        PackJob j{P->params[L.w].off, dst, ntaps, L.Cout, I, tr, pk.BN, pk.RB, pk.nchunks, pk.ntiles, ~(size_t)0, L.Cin, c0, tied};
-        P->pack_prefix.push_back(P->pack_total);
-        P->pack_jobs.push_back(j);
-        P->pack_total += (unsigned long long)ntaps * pk.nchunks * pk.ntiles * pk.BN * (pk.RB / 16);
-      };
-      add(L.tie_fu_off, 16, L.tie_Ca, 0, 0, 1, L.tie_pk_fu);
-      add(L.tie_du_off, L.tie_du_masked ? 9 : 16, L.tie_Ca, 0, 1, L.tie_du_masked ? 2 : 1, L.tie_pk_du);
-      if (L.tie_Cs > 0) {
-        add(L.tie_fs_off, 9, L.tie_Cs, L.tie_Ca, 0, 0, L.tie_pk_fs);
-        add(L.tie_ds_off, 9, L.tie_Cs, L.tie_Ca, 1, 0, L.tie_pk_ds);
-      }
-    }
+    if (L.tie)
+      tie_pack_jobs(TieImages{L.tie_pk_fu, L.tie_pk_du, L.tie_pk_fs, L.tie_pk_ds, L.tie_du_masked},
+                    TieOffsets{L.tie_fu_off, L.tie_du_off, L.tie_fs_off, L.tie_ds_off}, P->params[L.w].off, L.Cout, L.Cin, L.tie_Ca, L.tie_Cs,
+                    P->pack_jobs, P->pack_prefix, P->pack_total);
   }
   P->bn_jobs.clear(); P->bn_prefix.clear(); P->bn_total = 0;
   for (auto& b : P->bns) {

@@ -171,6 +171,57 @@ int tie_mask() {   // (read when a plan is built, so that one process can hold p
 Geom tie_geom_up(const ConvLayer& L) { return Geom{4, 4, 2, 1, true, L.N, L.IH / 2, L.IW / 2, L.tie_Ca, L.OH, L.OW, L.Cout}; }
 Geom tie_geom_skip(const ConvLayer& L) { return Geom{3, 3, 1, 1, false, L.N, L.IH, L.IW, L.tie_Cs, L.OH, L.OW, L.Cout}; }
 
+// A decoder layer of the form (nearest x2, concat, 3x3 stride 1 pad 1 + BatchNorm, no bias) over 2-byte elements whose sources all want a gradient.
+bool tie_eligible(const TieQuery& q) {
+  if (!(q.esz == 2 && !q.transposed && !q.stem && !q.head && !q.sliced && !q.accum_out && q.R == 3 && q.S == 3 && q.stride == 1 && q.pad == 1 &&
+        q.has_bn && !q.has_bias && q.nsrc >= 1 && q.up0_whole_grad))
+    return false;
+  if (!q.skips_plain_grad) return false;
+  // (narrow layers stay whole: below 64 channels a launch is a single K chunk and the thin kernels own the 16 / 32-channel decoder tail)
+  return q.Ca >= 64 && q.Ca % 8 == 0 && q.Cs % 8 == 0 && q.Cout >= 32 && (q.Cs == 0 || q.Cs >= 32);
+}
+
+TieImages tie_images(int dtype, const Geom& gu, const Geom& gs) {
+  TieImages im{};
+  std::vector<ConvArgs> v;
+  fwd_launches(gu, v);
+  im.pk_fu = conv_pack_info(v[0], dtype);
+  v.clear();
+  im.du_masked = false;
+  if (gu.Cout % 64 == 0) {   // one masked launch over the four parity planes: the planes are whole K chunks
+    ConvArgs am;
+    tied_dgrad_masked(gu, am);
+    DstDesc dd{}; dd.H = gu.IH; dd.W = gu.IW; dd.C = gu.Cin; dd.cn = gu.Cin; am.dst[0] = dd; am.ndst = 1;
+    if (conv_masked_eligible(am, dtype)) { im.du_masked = true; v.push_back(am); }
+  }
+  if (!im.du_masked) dgrad_launches(gu, v);
+  im.pk_du = conv_pack_info(v[0], dtype);
+  if (gs.Cin > 0) {
+    v.clear(); fwd_launches(gs, v);
+    im.pk_fs = conv_pack_info(v[0], dtype);
+    v.clear(); dgrad_launches(gs, v);
+    im.pk_ds = conv_pack_info(v[0], dtype);
+  }
+  return im;
+}
+
+// the tied images: 4x4 kernel over the upsampled source's channels, the plain 3x3 over the skip channels (training only: no fold)
+void tie_pack_jobs(const TieImages& im, const TieOffsets& at, size_t w_off, int Cout, int Cin, int Ca, int Cs, std::vector<PackJob>& jobs,
+                   std::vector<unsigned long long>& prefix, unsigned long long& total) {
+  auto add = [&](size_t dst, int ntaps, int I, int c0, int tr, int tied, const ConvPackInfo& pk) {
+    PackJob j{w_off, dst, ntaps, Cout, I, tr, pk.BN, pk.RB, pk.nchunks, pk.ntiles, ~(size_t)0, Cin, c0, tied};
+    prefix.push_back(total);
+    jobs.push_back(j);
+    total += (unsigned long long)ntaps * pk.nchunks * pk.ntiles * pk.BN * (pk.RB / 16);
+  };
+  add(at.fu, 16, Ca, 0, 0, 1, im.pk_fu);
+  add(at.du, im.du_taps(), Ca, 0, 1, im.du_masked ? 2 : 1, im.pk_du);
+  if (Cs > 0) {
+    add(at.fs, 9, Cs, Ca, 0, 0, im.pk_fs);
+    add(at.ds, 9, Cs, Ca, 1, 0, im.pk_ds);
+  }
+}
+
 // algorithmic multiply-accumulates of one pass (forward = dgrad = wgrad) over a conv layer
 double layer_macs(const ConvLayer& L) {
   return (double)L.N * L.OH * L.OW * L.Cout * (L.stem ? 3.0 * L.stem_k * L.stem_k : (double)L.Cin * (L.transposed ? 4.0 : (double)L.R * L.S));

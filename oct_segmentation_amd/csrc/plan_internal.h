@@ -67,6 +67,28 @@ void tied_dgrad_masked(const Geom& g, ConvArgs& a);
 int tie_mask();
 Geom tie_geom_up(const ConvLayer& L);
 Geom tie_geom_skip(const ConvLayer& L);
+// What decides whether a conv layer runs tied (ConvLayer::tie), what its four weight images look like and how they are packed: shared by
+// the plan builder (plan_build.cpp) and the single-layer door (conv_api.cpp, octseg_tied_layer_op), so that the door builds what the plan builds.
+struct TieQuery {
+  int esz;                                   // element size of the plan's dtype
+  bool transposed, stem, head, sliced, accum_out, has_bn, has_bias;
+  int R, S, stride, pad, nsrc;
+  bool up0_whole_grad;                       // source 0: nearest x2, the whole tensor (no channel slice), wants a gradient
+  bool skips_plain_grad;                     // every further source: full resolution, whole, wants a gradient
+  int Ca, Cs, Cout;                          // channels of source 0, of the others together, of the output
+};
+bool tie_eligible(const TieQuery& q);
+struct TieImages {
+  ConvPackInfo pk_fu, pk_du, pk_fs, pk_ds;   // forward up / data gradient up / forward skip / data gradient skip (the skip pair only with Cs > 0)
+  bool du_masked;                            // the up slice's data gradient is ONE masked launch over dy's parity planes (9-tap image)
+  int du_taps() const { return du_masked ? 9 : 16; }
+};
+TieImages tie_images(int dtype, const Geom& up, const Geom& skip);   // the Geoms of tie_geom_up / tie_geom_skip
+struct TieOffsets { size_t fu, du, fs, ds; };                        // bytes, relative to the base launch_pack_all receives
+// appends the layer's 2 (Cs == 0) or 4 jobs; w_off: the layer's 3x3 weight [9][Cout][Cin] in floats relative to the params base
+void tie_pack_jobs(const TieImages& im, const TieOffsets& at, size_t w_off, int Cout, int Cin, int Ca, int Cs, std::vector<PackJob>& jobs,
+                   std::vector<unsigned long long>& prefix, unsigned long long& total);
+int side_wgs();   // split-K width of the multi-tap weight gradients on the side stream (plan_backward.cpp)
 double layer_macs(const ConvLayer& L);
 bool geom_ok(int dtype, int Cin, int Cout, int R, int S, int stride, int transposed);   // the single-op entry points (octseg_conv2d_*)
 Geom op_geom(int N, int H, int W, int Cin, int Cout, int R, int S, int stride, int pad, int transposed);

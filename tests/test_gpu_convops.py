@@ -18,7 +18,8 @@ on the thin route and the single-op packer's (launch_pack_weight_image) on the i
 'mfma-16' names every 16-pixel-wide loop of conv_mfma_kernel (generic, resident, 1x1, the run9 / run9s slab rings, the four-tap masked loop of
 a wide ConvTranspose2d parity: the convT_wide case); which of the rings a case runs is choose()'s business and is not asserted.
 NOT covered: conv_mfma's wide-N tile (256 -> 256 on >= 1024 workgroups: its CPU reference takes tens of seconds; tests/test_gpu_ops.py and the
-whole-network tests keep it), the tied K4 images and per-source tap subsets (tests/test_gpu_tied.py), the 7x7 stem kernels.
+whole-network tests keep it).  The tied K4 images and per-source tap subsets have tests/test_gpu_tiedops.py (one pass at a time; whole networks:
+tests/test_gpu_tied.py), the 7x7 stem kernels and the stem im2col tests/test_gpu_stemops.py.
 """
 import copy
 import ctypes as C

@@ -110,6 +110,7 @@ hipError_t hipStreamCreateWithPriority(hipStream_t* st, unsigned f, int) { retur
 hipError_t hipStreamDestroy(hipStream_t) { return hipSuccess; }
 hipError_t hipDeviceGetStreamPriorityRange(int* lo, int* hi) { *lo = 0; *hi = -1; return hipSuccess; }
 hipError_t hipDeviceSynchronize(void) { return hipSuccess; }
+hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }   // (octseg_tied_layer_op waits for its job table's upload)
 hipError_t hipEventCreate(hipEvent_t* e) { *e = (hipEvent_t)(uintptr_t)(0x9000 + 16 * ++g_events); return hipSuccess; }
 hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { return hipEventCreate(e); }
 hipError_t hipEventDestroy(hipEvent_t) { return hipSuccess; }
