@@ -46,6 +46,9 @@
  *   octseg_stack_boundary / octseg_stack_distance / octseg_pair_distance_counts / _keys / _min / octseg_distance_scratch_bytes
  *                                      (no reference counterpart) exact squared Euclidean distance maps of the mask planes, the directed
  *                                      boundary-distance lists behind HD / HD95 / ASSD, the smallest distance between two classes
+ *   octseg_volume_components / octseg_volume_cleanup / octseg_lesions_scratch_bytes
+ *                                      (no reference counterpart) the connected components of a mask stack across its slices: labels, the 32
+ *                                      largest lesions per class with their extents, the per-slice area profile, the flicker filter
  *   octseg_volume_normalize            cv2.normalize(slice, None, 0, 255, NORM_MINMAX, CV_8U) + cvtColor(BGR2RGB) of every slice of a DICOM's
  *                                      pixel_array (src/data/convert_dicoms.py:71-81, src/app/tools/analysis.py:167-177)
  *   octseg_resize_pil_u8               data_processing's Image.open(p).resize(output_size), Pillow's default BICUBIC (src/data/utils.py:187)
@@ -348,6 +351,37 @@ int octseg_stack_components(const float* stack, int N, int H, int W, int channel
                             int* top, void* stream);
 int octseg_stack_cleanup(const float* stack, int N, int H, int W, int channels, int smooth_k, int keep, int min_area, int fill_holes, void* scratch,
                          size_t scratch_bytes, float* out, int* ncomp, int* top, void* stream);
+
+/* Lesions in 3-D (no reference counterpart: the app's get_analysis groups slices by class presence only; DESIGN.md section 5j, pinned to
+ * scipy.ndimage.label with an explicit 3 x 3 x 3 structure by tests/lesions_ref.py).  stack: device f32 [N][H][W][channels], any value != 0 is set.  A
+ * VOLUME is one channel of the stack, slices along N in the order given; channels are independent.  Inside a slice voxels are 8-connected.  across:
+ *   OCTSEG_ACROSS_OVERLAP  between adjacent slices only the same pixel connects (scipy structure S: S[1] = 1, S[0][1][1] = S[2][1][1] = 1, else 0);
+ *   OCTSEG_ACROSS_FULL     the full 3 x 3 x 3 structure (26-connected).
+ * The label of a lesion is 1 + n * H * W + y * W + x of its first voxel in raster order; background is 0.
+ * scratch: device, scratch_bytes >= octseg_lesions_scratch_bytes(channels, N, H, W) (0 for extents the calls refuse), 8-byte aligned.
+ *
+ * octseg_volume_components: optional outputs (null = skipped, at least one):
+ *   labels  int32 [channels][N][H][W];
+ *   nles    int32 [channels]: the number of lesions;
+ *   top     int32 [channels][32][8]: the 32 largest, voxels descending then first voxel ascending; columns voxels, first_voxel (n * H * W + y * W + x),
+ *           z0, z1, y0, y1, x0, x1 (inclusive bounds; z0 = first_voxel / (H * W)); rows beyond nles are zero;
+ *   profile int32 [channels][32][N]: the set pixels of ranked lesion r in slice n, zero outside z0..z1 and for rows beyond nles.
+ *
+ * octseg_volume_cleanup: out f32 [N][H][W][channels] (0.0 / 1.0, must not alias stack) = the lesions for which all three hold:
+ *   voxels >= t, t = the keep-th largest voxel count of the channel (0 with fewer lesions; ties at t all stay; keep = 0: no rank filter);
+ *   voxels >= min_voxels;
+ *   z1 - z0 + 1 >= min_slices (min_slices = 2 removes what shows in one slice only: the flicker filter).
+ * nles / top (optional) describe the kept lesions, in the layout above.
+ * Enqueue only, nothing is allocated, the stack is not modified.  Null stack / scratch / out, scratch too small or misaligned, no output requested,
+ * out == stack, negative keep / min_voxels, min_slices < 1, unknown across: OCTSEG_BAD_ARG; N, H, W <= 0, channels outside 1..16,
+ * N * H * W >= 2^31 - 1: OCTSEG_BAD_SHAPE.  Every refusal happens before any HIP call: nothing is launched and no output is touched then. */
+#define OCTSEG_ACROSS_OVERLAP 0
+#define OCTSEG_ACROSS_FULL 1
+size_t octseg_lesions_scratch_bytes(int channels, int N, int H, int W);
+int octseg_volume_components(const float* stack, int N, int H, int W, int channels, int across, void* scratch, size_t scratch_bytes, int* labels,
+                             int* nles, int* top, int* profile, void* stream);
+int octseg_volume_cleanup(const float* stack, int N, int H, int W, int channels, int across, int keep, int min_voxels, int min_slices, void* scratch,
+                          size_t scratch_bytes, float* out, int* nles, int* top, void* stream);
 
 /* Boundary distances (no reference counterpart: the reference scores overlap only; what is restated here are the definitions of DESIGN.md
  * section 5i, pinned to scipy.ndimage by tests/distance_ref.py).  stack / src / dst: device f32 [N][H][W][channels], any value != 0 is set; a plane

@@ -147,6 +147,11 @@ SYMBOLS = {
     'octseg_components_scratch_bytes': (C.c_size_t, [C.c_int] * 3),
     'octseg_stack_components': (C.c_int, [_P] + [C.c_int] * 4 + [_P, C.c_size_t, _P, _P, _P, _P]),
     'octseg_stack_cleanup': (C.c_int, [_P] + [C.c_int] * 8 + [_P, C.c_size_t, _P, _P, _P, _P]),
+    # float32 mask stack -> connected components across the slices (labels, count, the 32 largest with extents, per-slice profile) and the stack
+    # filtered by voxel count, rank and slice span (csrc/lesions.hip)
+    'octseg_lesions_scratch_bytes': (C.c_size_t, [C.c_int] * 4),
+    'octseg_volume_components': (C.c_int, [_P] + [C.c_int] * 5 + [_P, C.c_size_t, _P, _P, _P, _P, _P]),
+    'octseg_volume_cleanup': (C.c_int, [_P] + [C.c_int] * 8 + [_P, C.c_size_t, _P, _P, _P, _P]),
     # float32 mask stacks -> boundary planes, exact squared distance maps, per (slice, channel pair) counts, keyed distance lists and the
     # minimum with its location (csrc/distance.hip)
     'octseg_distance_scratch_bytes': (C.c_size_t, [C.c_int] * 6),

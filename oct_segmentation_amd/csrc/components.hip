@@ -35,6 +35,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "unionfind.h"   // u64, inmask, ctz64, runlen, runmask, find_root, unite
 
 namespace octseg {
 
@@ -48,17 +49,10 @@ constexpr int SEL_NT = OCTSEG_SEL_NT;     // workgroup of select_kernel (any pow
 constexpr int TOPK = 8, TCOL = 6;
 constexpr unsigned MAX_GRID = 1u << 20;
 
-typedef unsigned long long u64;
-
 struct Geo { int H, W, W64, HW; };
 
 struct Elem { int k, a; int lo[7], hi[7]; };   // cv2.getStructuringElement(MORPH_ELLIPSE, (k, k)): row i is set on columns lo[i]..hi[i]; anchor a
 
-// the bits of word j that lie inside the frame (j < W64, so at least one)
-__device__ __forceinline__ u64 inmask(int j, int W) {
-  const int n = W - j * 64;
-  return n >= 64 ? ~0ull : ((1ull << n) - 1ull);
-}
 // word j of row y as the labelling sees it: 0 outside the frame; inv = the complement inside the frame
 __device__ __forceinline__ u64 rdw(const u64* __restrict__ plane, int y, int j, const Geo& g, int inv) {
   if (y < 0 || y >= g.H || j < 0 || j >= g.W64) return 0ull;
@@ -70,35 +64,6 @@ __device__ __forceinline__ u64 rdm(const u64* __restrict__ plane, int y, int j, 
   if (y < 0 || y >= g.H || j < 0 || j >= g.W64) return ero ? ~0ull : 0ull;
   const u64 w = plane[(size_t)y * g.W64 + j];
   return ero ? w | ~inmask(j, g.W) : w;
-}
-__device__ __forceinline__ int ctz64(u64 v) { return __ffsll((long long)v) - 1; }            // v != 0
-// length of the run of set bits that starts at bit s (bit s is set)
-__device__ __forceinline__ int runlen(u64 c, int s) {
-  const u64 z = ~(c >> s);                       // s > 0 shifts zeros in at the top, so z != 0 then
-  return (s == 0 && z == 0ull) ? 64 : min(ctz64(z), 64 - s);
-}
-__device__ __forceinline__ u64 runmask(int s, int len) { return (len == 64 ? ~0ull : ((1ull << len) - 1ull)) << s; }
-
-// walks strictly downwards (parent[x] < x for a non-root): at most H * W steps
-__device__ __forceinline__ int find_root(const int* par, int x) {
-  for (;;) {
-    const int q = __hip_atomic_load(par + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (q == x) return x;
-    x = q;
-  }
-}
-// Label-equivalence union.  Every round either links a root (return) or continues with a pair that is strictly smaller in its larger member:
-// labels only ever decrease, so the loop ends.
-__device__ __forceinline__ void unite(int* par, int a, int b) {
-  for (;;) {
-    a = find_root(par, a);
-    b = find_root(par, b);
-    if (a == b) return;
-    if (a < b) { const int t = a; a = b; b = t; }          // a > b: the larger root goes under the smaller
-    const int old = atomicMin(par + a, b);
-    if (old == a) return;                                  // a was a root and now points at b
-    a = old;                                               // a had been linked meanwhile: its former parent and b must still meet
-  }
 }
 
 }  // namespace

@@ -366,6 +366,15 @@ hipError_t launch_stack_components(const float* stack, int N, int H, int W, int 
 hipError_t launch_stack_cleanup(const float* stack, int N, int H, int W, int C, int smooth_k, int keep, int min_area, int fill_holes, void* scratch,
                                 float* out, int* ncomp, int* top, hipStream_t st);
 
+// lesions in 3-D (lesions.hip): the connected components of every channel's volume across the slices (8-connected inside a slice; between slices
+// the same pixel only, or with full != 0 the 3 x 3), the 32 largest with their extents, the per-slice area profile, and the voxel / rank / slice-span
+// filter.  scratch: lesions_scratch_bytes(C, N, H, W) device bytes; labels / nles / top / profile are optional (null = skipped)
+size_t lesions_scratch_bytes(size_t channels, int N, int H, int W);
+hipError_t launch_volume_components(const float* stack, int N, int H, int W, int C, int full, void* scratch, int* labels, int* nles, int* top,
+                                    int* profile, hipStream_t st);
+hipError_t launch_volume_cleanup(const float* stack, int N, int H, int W, int C, int full, int keep, int min_voxels, int min_slices, void* scratch,
+                                 float* out, int* nles, int* top, hipStream_t st);
+
 // boundary distances (distance.hip): the boundary of every plane, the exact squared Euclidean distance map (column pass + row minimum in LDS), and
 // per (slice, pair of channels) the counts, the keyed list of d2 at the query pixels, and their minimum with its location.  scratch:
 // distance_scratch_bytes(N, H, W, Ca, Cb, pairs) device bytes (one-stack calls: Cb = 0, pairs = 0).  part / to: 0 set, 1 clear, 2 boundary

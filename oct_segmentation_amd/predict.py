@@ -289,6 +289,15 @@ def _main_volume(cfg, device, dtypes, log):
             json.dump(res.data, f)
     if res.plaque is not None:
         _save_plaque(res.plaque, res.stack, cfg['classes'], save_dir)
+    if bool(cfg.get('lesions', False)):
+        _save_lesions(res.stack, names, save_dir)
+
+
+def _save_lesions(stack, names, save_dir):
+    """``lesions=true``: ``{save_dir}/lesions.json``, ``lesions.lesion_report`` of the stack, slices in the order given."""
+    from .lesions import lesion_report
+    with open(os.path.join(save_dir, 'lesions.json'), 'w') as f:
+        json.dump(lesion_report(stack, names), f)
 
 
 def _save_plaque(report, stack, classes, save_dir):
@@ -319,6 +328,8 @@ def main(argv=None):
     largest components, hole fill) before it is rendered and measured;
     ``plaque`` (default false): also write ``{save_dir}/plaque.json``, the polar plaque report of the same stack (``polar.plaque_report``: lipid
     arc, cap thickness where lipid lies behind it), and ``plaque_carpet.png`` (``polar.carpet_view``), slices in the order ``analysis`` uses;
+    ``lesions`` (default false): also write ``{save_dir}/lesions.json``, the 3-D lesion report of the same stack (``lesions.lesion_report``:
+    components across the slices, their length, voxels, bounding box and area profile), slices in the order ``analysis`` uses;
     ``device_resize`` (default true): ``RGB`` and ``L`` files go up at source size and ``data_processing``'s ``Image.resize`` runs on the GPU
     (``pullback.resize_pil_u8``, byte-identical; false restores the host resize for every file).  A ``data_dir`` that is a ``.npy`` file is a
     raw volume (a DICOM's ``pixel_array``) and goes through ``pullback.analyze_pullback``: see ``_main_volume``."""
@@ -372,6 +383,9 @@ def main(argv=None):
         order = sorted(range(len(paths)), key=lambda i: os.path.basename(paths[i]))
         ordered = stack[torch.tensor(order, device=stack.device)]
         _save_plaque(plaque_report(ordered, [names[i] for i in order]), ordered, cfg['classes'], str(cfg['save_dir']))
+    if bool(cfg.get('lesions', False)):
+        order = sorted(range(len(paths)), key=lambda i: os.path.basename(paths[i]))
+        _save_lesions(stack[torch.tensor(order, device=stack.device)], [names[i] for i in order], str(cfg['save_dir']))
     log.info(f'Overall computation time: {time.time() - start:.1f} s')
     log.info('Complete')
     return 0

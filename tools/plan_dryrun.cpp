@@ -6,7 +6,7 @@
 // encoder pair at the smallest legal frame, the benchmark frame and a non-square one, in all three dtypes, with no kernel launched
 // (no GPU needed).  A subset of the plans is then driven through octseg_net_forward / _backward / _backward_sliced / octseg_optim_step and
 // the graph-captured eval forward, and the class-activation-map path (frozen forward, seeded backward, map launches) against tools/hip_host_stubs.cpp, a recording stand-in for the HIP runtime that checks every launch
-// geometry and every memset / copy range; the boundary-distance entry points (csrc/distance.hip) are driven the same way, from a 1 x 1 frame to
+// geometry and every memset / copy range; the boundary-distance entry points (csrc/distance.hip) and the 3-D lesion entry points (csrc/lesions.hip) are driven the same way, from a 1 x 1 frame to
 // 4096 x 4096.  Exit code 0 = the sanitizers and the stubs saw nothing.
 #include <cstdio>
 #include <cstring>
@@ -157,6 +157,59 @@ int exercise_distance() {
   if (octseg_distance_scratch_bytes(1, 4097, 8, 1, 0, 0) != 0 || octseg_distance_scratch_bytes(1, 8, 8, 17, 0, 0) != 0) return 38;
   return 0;
 }
+
+// The 3-D lesion entry points (csrc/lesions.hip, csrc/lesions_api.cpp) against the stubs: the scratch carving, the two memsets (lesion counters,
+// profile) inside their ranges and every grid, from a single voxel to a volume just under 2^31 - 1 voxels; then what they must refuse.
+int exercise_lesions() {
+  char* base = (char*)(uintptr_t)0x300000000000ull;
+  auto carve = [&](size_t bytes) { char* r = base; base += (bytes + 4095) / 4096 * 4096 + 4096; dry_register_range(r, bytes); return r; };
+  const int shapes[][4] = {{1, 1, 1, 1}, {5, 97, 130, 5}, {186, 750, 750, 4}, {2047, 1024, 1024, 16}};
+  for (auto& sh : shapes) {
+    dry_clear_ranges();
+    const int N = sh[0], H = sh[1], W = sh[2], C = sh[3];
+    const size_t need = octseg_lesions_scratch_bytes(C, N, H, W);
+    if (need == 0 || need <= octseg_lesions_scratch_bytes(1, N, H, W) - (C == 1)) return 40;
+    const size_t elems = (size_t)N * H * W * C;
+    float* a = (float*)carve(elems * 4);
+    float* out = (float*)carve(elems * 4);
+    int* labels = (int*)carve(elems * 4);
+    void* scratch = carve(need);
+    int* nles = (int*)carve((size_t)C * 4);
+    int* top = (int*)carve((size_t)C * 32 * 8 * 4);
+    int* profile = (int*)carve((size_t)C * 32 * N * 4);
+    void* st = (void*)(uintptr_t)0x5000;
+    for (int across = 0; across < 2; ++across) {
+      if (octseg_volume_components(a, N, H, W, C, across, scratch, need, labels, nles, top, profile, st) != 0) {
+        fprintf(stderr, "volume_components: %s\n", octseg_last_error());
+        return 41;
+      }
+      if (octseg_volume_components(a, N, H, W, C, across, scratch, need, labels, nullptr, nullptr, nullptr, st) != 0) return 41;
+      if (octseg_volume_components(a, N, H, W, C, across, scratch, need, nullptr, nullptr, nullptr, profile, st) != 0) return 41;
+      if (octseg_volume_cleanup(a, N, H, W, C, across, 3, 2, 2, scratch, need, out, nles, top, st) != 0) {
+        fprintf(stderr, "volume_cleanup: %s\n", octseg_last_error());
+        return 42;
+      }
+      if (octseg_volume_cleanup(a, N, H, W, C, across, 0, 0, 1, scratch, need, out, nullptr, nullptr, st) != 0) return 42;
+    }
+    // refused before anything is enqueued
+    const unsigned long long before = dry_launches() + dry_memops();
+    if (octseg_volume_components(a, N, H, W, C, 0, scratch, need - 1, labels, nles, top, profile, st) == 0 ||
+        octseg_volume_components(a, N, H, W, C, 2, scratch, need, labels, nles, top, profile, st) == 0 ||
+        octseg_volume_components(a, N, H, W, 17, 0, scratch, need, labels, nles, top, profile, st) == 0 ||
+        octseg_volume_components(a, N, H, W, C, 0, scratch, need, nullptr, nullptr, nullptr, nullptr, st) == 0 ||
+        octseg_volume_components(a, N, H, W, C, 0, (char*)scratch + 4, need, labels, nles, top, profile, st) == 0 ||
+        octseg_volume_cleanup(a, N, H, W, C, 0, 0, 0, 0, scratch, need, out, nles, top, st) == 0 ||
+        octseg_volume_cleanup(a, N, H, W, C, 0, -1, 0, 2, scratch, need, out, nles, top, st) == 0 ||
+        octseg_volume_cleanup(a, N, H, W, C, 0, 0, -1, 2, scratch, need, out, nles, top, st) == 0 ||
+        octseg_volume_cleanup(a, N, H, W, C, 0, 0, 0, 2, scratch, need, a, nles, top, st) == 0 ||
+        octseg_volume_cleanup(a, N, H, W, C, 0, 0, 0, 2, scratch, need, nullptr, nles, top, st) == 0)
+      return 43;
+    if (dry_launches() + dry_memops() != before) { fprintf(stderr, "a refused lesion call enqueued work\n"); return 44; }
+  }
+  if (octseg_lesions_scratch_bytes(1, 2048, 1024, 1024) != 0 || octseg_lesions_scratch_bytes(17, 2, 8, 8) != 0 || octseg_lesions_scratch_bytes(1, 0, 8, 8) != 0)
+    return 45;
+  return 0;
+}
 }  // namespace
 
 int main() {
@@ -252,6 +305,7 @@ int main() {
     if (octseg_plan_create(b, &q) == 0) { fprintf(stderr, "a bad descriptor was accepted\n"); return 7; }
   for (int dt = 0; dt < 3; ++dt) checksum += octseg_conv2d_scratch_bytes(dt, 2, 64, 64, 24, 40, 3, 3) + octseg_conv2d_scratch_bytes(dt, 1, 8, 8, 2048, 512, 1, 1);
   if (const int rc = exercise_distance()) { fprintf(stderr, "exercise_distance -> %d\n", rc); return rc; }
+  if (const int rc = exercise_lesions()) { fprintf(stderr, "exercise_lesions -> %d\n", rc); return rc; }
   if (dry_errors() != 0) { fprintf(stderr, "%llu launch / memory-range violations\n", dry_errors()); return 8; }
   printf("plan_dryrun: %d plans built, %d of them run through forward / backward / optimizer with recording HIP stubs (%llu launches, %llu memory "
          "operations checked) under ASan + UBSan, checksum %llu, 0 errors, launch fingerprint %016llx\n", plans, executed, dry_launches(), dry_memops(), checksum,
