@@ -31,6 +31,8 @@
  *                                      (dataset.py:111-118,125)
  *   octseg_mask_assemble               the per-frame epilogue of segment(): threshold, cv2 INTER_NEAREST resize to output_size,
  *                                      write into mask[:, :, CLASS_ID - 1] (src/predict.py:92-100, data/utils.py:16-33)
+ *   octseg_vote_assemble               (no reference counterpart) the same epilogue voted by M members, the folds of
+ *                                      src/data/convert_int_to_cv.py:73-93 and flipped / rotated views: mask, mean probability, dissent map, counts
  *   octseg_render_results              save_results: closing, ring, blur, two alpha pastes per class into the frame, the flat colour mask
  *                                      (src/data/utils.py:195-235, get_img_mask_union_pil src/models/smp/utils.py:203-213)
  *   octseg_epoch_panels                log_predict_model_on_epoch, the per-epoch image | ground truth | prediction strips and the two W&B label
@@ -210,6 +212,42 @@ int octseg_augment(const float* img, const float* mask, float* img_out, float* m
  * min(floor(i * (1 / (out / in))), in - 1), what the reference's cv2.resize call computes); null = floor((i + 0.5) * H / out_h). */
 int octseg_mask_assemble(const float* logits, int N, int classes, int H, int W, int ch, float* out, int out_h, int out_w,
                          int out_channels, int out_ch, const int* row_index, const int* col_index, void* stream);
+
+/* Voted serving epilogue (no reference counterpart: the reference trains five folds per class, src/data/convert_int_to_cv.py:73-93, and serves
+ * one; DESIGN.md section 5k, pinned to tests/vote_ref.py): ONE mask from M member networks -- folds, and every fold on flipped / rotated views of
+ * the frame -- with the map of where they disagree.  One launch per (batch of frames, output class).
+ *
+ * Members: logits / classes / ch / view are HOST arrays [M], 1 <= M <= OCTSEG_VOTE_MAX_MEMBERS; they travel to the kernel in its argument, by
+ * value (no table upload, no synchronisation).  logits[m]: device f32 NCHW [N][classes[m]][Hm][Wm], of which channel ch[m] votes; view[m] in 0..7.
+ * View code v = a + 2 b + 4 t.  The view of a frame X[H][W] is made in this order: transpose if t (needs H == W), reverse the rows if b, reverse
+ * the columns if a (torch: Y = X.transpose(-1, -2) if t; Y = Y.flip(-2) if b; Y = Y.flip(-1) if a) -- the eight codes are the dihedral group D4.
+ * A member's logits live in ITS VIEW's coordinates; H, W are the extents of the un-viewed frame, a member with t is [N][classes][W][H] (the
+ * same extents).  The kernel undoes the view while it reads: for the source pixel (sy, sx) of the un-viewed frame, (p, q) = t ? (sx, sy) : (sy, sx),
+ * (Ht, Wt) = t ? (W, H) : (H, W), and the member is read at (b ? Ht - 1 - p : p, a ? Wt - 1 - q : q) with row length Wt.
+ * Resize: exactly octseg_mask_assemble's rule -- row_index[out_h] / col_index[out_w] device int32 tables that index the un-viewed frame, null =
+ * floor((i + 0.5) * H / out_h); indices are clamped on the device.
+ *
+ * Per output pixel, with s_m = the engine's one fp32 sigmoid of member m's logit (the one behind octseg_mask_assemble and the Dice kernel):
+ *   votes = #{m : s_m > 0.5f};
+ *   mode OCTSEG_VOTE_SOFT:     pbar = (s_0 + s_1 + ... + s_{M-1}) / (float)M, the sum in f32 in member order; mask = pbar > 0.5f;
+ *   mode OCTSEG_VOTE_MAJORITY: mask = 2 * votes > M -- a tie is NOT set; pbar as above for the optional output;
+ *   dissent = mask ? M - votes : votes, the number of members whose own threshold differs from the written mask.
+ * Outputs, channel-last like the stack, written at channel out_ch only (other channels are left untouched):
+ *   out     f32   [N][out_h][out_w][out_channels], 0.0 / 1.0; required;
+ *   prob    f32   same shape, pbar; nullable;
+ *   dissent uint8 same shape; nullable;
+ *   stats   int32 [N][4], nullable: over the output pixels of each frame, the number set, disputed (0 < votes < M), disputed and set, and the sum
+ *           of dissent.  Integers only, so they are exact and reproducible; cleared on the stream by the call, then one atomic per workgroup.
+ * With M == 1 and view 0, out equals octseg_mask_assemble's bit for bit.
+ * Enqueue only (one clear of stats, one launch).  Refused before any HIP call, octseg_last_error() naming the offending member: a null required
+ * pointer or member pointer, mode not 0 / 1: OCTSEG_BAD_ARG; M outside 1..64, an extent <= 0, more than 65535 frames, ch[m] outside
+ * [0, classes[m]), out_ch outside [0, out_channels), view[m] outside 0..7, a t view with H != W: OCTSEG_BAD_SHAPE. */
+#define OCTSEG_VOTE_MAX_MEMBERS 64
+#define OCTSEG_VOTE_SOFT 0
+#define OCTSEG_VOTE_MAJORITY 1
+int octseg_vote_assemble(const float* const* logits, const int* classes, const int* ch, const int* view, int M, int N, int H, int W, int mode,
+                         float* out, int out_h, int out_w, int out_channels, int out_ch, const int* row_index, const int* col_index, float* prob,
+                         uint8_t* dissent, int* stats, void* stream);
 
 /* Input half of the pipeline (reference src/models/smp/dataset.py:108-127, src/data/utils.py:159-166): the decoded uint8 arrays go to the
  * device as they are and come out as the float32 NCHW batch octseg_net_forward takes.  Integer arithmetic from host-made tables: the result

@@ -321,6 +321,19 @@ hipError_t launch_relu(int dtype, const void* in, const void* mask, void* out, s
 hipError_t launch_mask_assemble(const float* logits, int N, int C, int SH, int SW, int ch, float* out, int OH, int OW, int OC, int out_ch,
                                 const int* rows, const int* cols, hipStream_t st);
 
+// serving, voted (vote.hip): one mask from M members (folds x views), the mean probability, the dissent map and per-frame counts in one launch.
+// The member table travels in the kernel argument by value.  view = a + 2 b + 4 t (transpose, then rows reversed, then columns reversed); mode 0
+// soft (mean probability > 0.5), 1 majority (a tie is not set); prob / dissent / stats are optional (null = skipped), stats is cleared on the stream
+constexpr int VOTE_MAX_MEMBERS = 64;
+struct VoteArgs {
+  const float* z[VOTE_MAX_MEMBERS]; int classes[VOTE_MAX_MEMBERS], ch[VOTE_MAX_MEMBERS], view[VOTE_MAX_MEMBERS];
+  int M, N, H, W, mode;
+  float* out; int OH, OW, OC, out_ch;
+  const int* rows; const int* cols;
+  float* prob; uint8_t* dissent; int* stats;
+};
+hipError_t launch_vote_assemble(const VoteArgs& a, hipStream_t st);
+
 // on-GPU training augmentation (augment.hip): AUG_NPARAM floats per frame, layout in the kernel's header comment
 constexpr int AUG_NPARAM = 36;
 hipError_t launch_augment(const float* img, const float* mask, float* img_out, float* mask_out, const float* params, int B, int C, int H,

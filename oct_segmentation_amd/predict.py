@@ -270,6 +270,9 @@ def _main_volume(cfg, device, dtypes, log):
     ``pullback.analyze_pullback``.  Slice ``k`` (from 1) is written as ``{stem}_{k:03d}_mask.png`` / ``_overlay.png``, the names
     convert_dicoms gives its frames."""
     from .pullback import analyze_pullback
+    folds, tta, _ = _vote_keys(cfg)
+    if folds or tta != 'none':      # analyze_pullback segments with one network per class: refuse, do not quietly serve an unvoted stack
+        raise ValueError('folds / tta vote over image files only: a .npy volume goes through pullback.analyze_pullback, which does not vote')
     path = str(cfg['data_dir'])
     volume = np.load(path)
     stem = os.path.basename(path).split('.')[0]
@@ -309,6 +312,30 @@ def _save_plaque(report, stack, classes, save_dir):
     Image.fromarray(carpet_view(polar_profile(stack), classes)).save(os.path.join(save_dir, 'plaque_carpet.png'))
 
 
+def _vote_keys(cfg):
+    """The three voting keys: ``folds`` (default false), ``tta`` (``none`` | ``flips`` | ``d4``, default ``none``), ``vote`` (``soft`` | ``majority``,
+    default ``soft``).  Unknown names are refused here, before anything is loaded."""
+    folds, tta, mode = bool(cfg.get('folds', False)), str(cfg.get('tta') or 'none'), str(cfg.get('vote') or 'soft')
+    if tta not in ('none', 'flips', 'd4'):
+        raise ValueError(f'tta must be none, flips or d4, got {tta!r}')
+    if mode not in ('soft', 'majority'):
+        raise ValueError(f'vote must be soft or majority, got {mode!r}')
+    return folds, tta, mode
+
+
+def _save_vote(voted, paths, names, classes, save_dir):
+    """A voted prediction's own files: ``{save_dir}/vote.json`` (``vote.vote_report``, slices in sorted file-name order, as ``analysis`` uses) and,
+    where the dissent maps were asked for, ``{name}_dissent.png`` per frame (``vote.dissent_images``)."""
+    from .vote import dissent_images, vote_report
+    order = sorted(range(len(paths)), key=lambda i: os.path.basename(paths[i]))
+    ordered = voted._replace(stats=voted.stats[torch.tensor(order, device=voted.stats.device)])
+    with open(os.path.join(save_dir, 'vote.json'), 'w') as f:
+        json.dump(vote_report(ordered, [names[i] for i in order], classes), f)
+    if voted.dissent is not None:
+        for name, img in zip(names, dissent_images(voted, classes)):
+            Image.fromarray(img).save(f'{save_dir}/{name}_dissent.png')
+
+
 def _image_paths(data_path):
     """data/utils.py:175-178: one file, or the directory's ``*.[pj][np][ge]*`` (png, jpg, jpeg ...)."""
     if os.path.isfile(data_path):
@@ -330,6 +357,10 @@ def main(argv=None):
     arc, cap thickness where lipid lies behind it), and ``plaque_carpet.png`` (``polar.carpet_view``), slices in the order ``analysis`` uses;
     ``lesions`` (default false): also write ``{save_dir}/lesions.json``, the 3-D lesion report of the same stack (``lesions.lesion_report``:
     components across the slices, their length, voxels, bounding box and area profile), slices in the order ``analysis`` uses;
+    ``folds`` (default false), ``tta`` (``none`` | ``flips`` | ``d4``, default ``none``), ``vote`` (``soft`` | ``majority``, default ``soft``): with
+    ``folds`` true or a ``tta`` the stack is voted by every ``fold_<k>`` network of a class on every view (``vote.segment_stack_voted``) and
+    ``{save_dir}/vote.json`` (``vote.vote_report``) is written, slices in the order ``analysis`` uses; ``dissent_maps`` (default false) adds
+    ``{name}_dissent.png`` per frame, grayscale, the maximum over the classes of ``dissent * (255 // members)``;
     ``device_resize`` (default true): ``RGB`` and ``L`` files go up at source size and ``data_processing``'s ``Image.resize`` runs on the GPU
     (``pullback.resize_pil_u8``, byte-identical; false restores the host resize for every file).  A ``data_dir`` that is a ``.npy`` file is a
     raw volume (a DICOM's ``pixel_array``) and goes through ``pullback.analyze_pullback``: see ``_main_volume``."""
@@ -363,9 +394,22 @@ def main(argv=None):
     names = [os.path.basename(p).split('.')[0] for p in paths]
     log.info(f'Number of images: {len(names)}')
     start_inference = time.time()
-    stack = segment_stack(images, cfg['output_size'], cfg['classes'], str(cfg['models_dir']), device=device,
-                          batch_size=int(cfg.get('batch_size', 8)), compute_dtype=dtypes[str(cfg.get('compute_dtype', 'bf16'))],
-                          use_graph=bool(cfg.get('use_graph', False)), device_preprocess=True)
+    folds, tta, vote_mode = _vote_keys(cfg)
+    voted = None
+    if bool(cfg.get('dissent_maps', False)) and not (folds or tta != 'none'):
+        raise ValueError('dissent_maps=true needs a vote: folds=true or tta=flips | d4')
+    if folds or tta != 'none':
+        from .vote import segment_stack_voted
+        voted = segment_stack_voted(images, cfg['output_size'], cfg['classes'], str(cfg['models_dir']), tta=tta, folds=folds, mode=vote_mode,
+                                    want_dissent=bool(cfg.get('dissent_maps', False)), device=device, batch_size=int(cfg.get('batch_size', 8)),
+                                    compute_dtype=dtypes[str(cfg.get('compute_dtype', 'bf16'))])
+        stack = voted.stack
+    else:
+        stack = segment_stack(images, cfg['output_size'], cfg['classes'], str(cfg['models_dir']), device=device,
+                              batch_size=int(cfg.get('batch_size', 8)), compute_dtype=dtypes[str(cfg.get('compute_dtype', 'bf16'))],
+                              use_graph=bool(cfg.get('use_graph', False)), device_preprocess=True)
+    if voted is not None:
+        _save_vote(voted, paths, names, cfg['classes'], str(cfg['save_dir']))
     if bool(cfg.get('clean', False)):
         from .cleanup import clean_stack
         stack = clean_stack(stack)
