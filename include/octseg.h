@@ -33,6 +33,8 @@
  *                                      write into mask[:, :, CLASS_ID - 1] (src/predict.py:92-100, data/utils.py:16-33)
  *   octseg_vote_assemble               (no reference counterpart) the same epilogue voted by M members, the folds of
  *                                      src/data/convert_int_to_cv.py:73-93 and flipped / rotated views: mask, mean probability, dissent map, counts
+ *   octseg_logit_histogram             (no reference counterpart) per frame and class, the 256-bin histogram of the predicted probability over
+ *                                      the truth-negative and over the truth-positive pixels: every threshold's tp / fp / fn / tn by suffix sums
  *   octseg_render_results              save_results: closing, ring, blur, two alpha pastes per class into the frame, the flat colour mask
  *                                      (src/data/utils.py:195-235, get_img_mask_union_pil src/models/smp/utils.py:203-213)
  *   octseg_epoch_panels                log_predict_model_on_epoch, the per-epoch image | ground truth | prediction strips and the two W&B label
@@ -248,6 +250,33 @@ int octseg_mask_assemble(const float* logits, int N, int classes, int H, int W, 
 int octseg_vote_assemble(const float* const* logits, const int* classes, const int* ch, const int* view, int M, int N, int H, int W, int mode,
                          float* out, int out_h, int out_w, int out_channels, int out_ch, const int* row_index, const int* col_index, float* prob,
                          uint8_t* dissent, int* stats, void* stream);
+
+/* Logit histograms (no reference counterpart: the reference scores per-class DSC at the one threshold 0.5, src/models/smp/utils.py:13-36; DESIGN.md
+ * section 5l, pinned to tests/curves_ref.py): per frame and class, how many pixels fall into each of OCTSEG_CURVE_BINS probability bins, counted
+ * once over the truth-negative and once over the truth-positive pixels.  One streaming pass over logits and target; every threshold's confusion
+ * counts, and from them ROC, precision-recall, reliability and the DSC-optimal cut, follow on the host from 2 KB per frame and class.
+ *
+ *   logits  device f32 NCHW [N][classes][H][W];
+ *   target  device f32 NCHW [N][classes][H][W], octseg_dice_forward's target: a pixel is POSITIVE iff its value is != 0;
+ *   hist    device int32 [N][classes][2][OCTSEG_CURVE_BINS], label-major: hist[n][c][0][j] counts the truth-negative pixels of frame n, class c in
+ *           bin j, hist[n][c][1][j] the truth-positive ones.  The call clears it on the stream, then launches once; required.
+ *
+ * Bin rule, per pixel, all in f32:
+ *   p   = the engine's one fp32 sigmoid of the logit z (the one behind octseg_mask_assemble, octseg_vote_assemble and the Dice kernel):
+ *         e = expf(-|z|); p = z >= 0 ? 1 / (1 + e) : e / (1 + e);
+ *   bin = clamp((int)ceilf(p * 256.0f) - 1, 0, 255).  The product is by a power of two and therefore exact.
+ * Bin j holds p in (j / 256, (j + 1) / 256], and p == 0 falls into bin 0.  A pixel is predicted at threshold k / 256, k = 1 .. 255, iff
+ * bin >= k, which is exactly p > k / 256 in f32: tp(k) = sum of hist[n][c][1][j] over j >= k, fp(k) the same of hist[n][c][0], fn and tn the
+ * sums over j < k.  At k = 128 this is the engine's `sigmoid > 0.5f` pixel for pixel: z = +-0 and |z| = 1e-9 give p == 0.5 exactly, bin 127,
+ * not set.  k = 0 (every pixel set) and k = 256 (none) follow from the row totals; a row's 512 counts sum to H * W.
+ * Integers only: the counts are exact and do not depend on the order in which workgroups finish.
+ *
+ * Enqueue only; logits and target are read, never written, and may be any 4-byte-aligned device addresses.  Every refusal happens before any HIP
+ * call, launches nothing and leaves hist untouched.  Null pointer: OCTSEG_BAD_ARG; N, classes, H or W <= 0, H * W >= 2^31, or N * classes > 65535
+ * (one launch takes a plane per grid row): OCTSEG_BAD_SHAPE. */
+#define OCTSEG_CURVE_BINS 256
+int octseg_logit_histogram(const float* logits, const float* target, int N, int classes, int H, int W,
+                           int* hist, void* stream);
 
 /* Input half of the pipeline (reference src/models/smp/dataset.py:108-127, src/data/utils.py:159-166): the decoded uint8 arrays go to the
  * device as they are and come out as the float32 NCHW batch octseg_net_forward takes.  Integer arithmetic from host-made tables: the result

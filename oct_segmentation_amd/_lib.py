@@ -131,6 +131,8 @@ SYMBOLS = {
     'octseg_mask_assemble': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     # M members' logits (host arrays of device pointers, classes, channels, view codes) -> voted mask, mean probability, dissent, counts (csrc/vote.hip)
     'octseg_vote_assemble': (C.c_int, [_P, _P, _P, _P] + [C.c_int] * 5 + [_P] + [C.c_int] * 4 + [_P] * 6),
+    # logits + target -> int32 [N, classes, 2, 256] probability histograms per truth label (csrc/curves.hip)
+    'octseg_logit_histogram': (C.c_int, [_P, _P] + [C.c_int] * 4 + [_P, _P]),
     # uint8 frames / masks -> float32 NCHW batch (csrc/ingest.hip)
     'octseg_ingest_image': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P]),
     'octseg_ingest_mask': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P]),

@@ -334,6 +334,11 @@ struct VoteArgs {
 };
 hipError_t launch_vote_assemble(const VoteArgs& a, hipStream_t st);
 
+// operating curves (curves.hip): hist int32 [N][classes][2][CURVE_BINS], label-major (0 = truth-negative, 1 = truth-positive pixels, target != 0),
+// bin = clamp((int)ceilf(sigmoid_acc(z) * 256) - 1, 0, 255); cleared on the stream, then one launch.  N * classes <= 65535, H * W < 2^31
+constexpr int CURVE_BINS = 256;
+hipError_t launch_logit_histogram(const float* logits, const float* target, int N, int classes, int H, int W, int* hist, hipStream_t st);
+
 // on-GPU training augmentation (augment.hip): AUG_NPARAM floats per frame, layout in the kernel's header comment
 constexpr int AUG_NPARAM = 36;
 hipError_t launch_augment(const float* img, const float* mask, float* img_out, float* mask_out, const float* params, int B, int C, int H,

@@ -149,12 +149,17 @@ def _resize_frames_on_device(frames, lo, hi, size):
 
 
 def segment_stack(images, output_size, classes, models_dir, device='cuda', batch_size=8, compute_dtype=torch.bfloat16, use_graph=False,
-                  device_preprocess=False):
+                  device_preprocess=False, thresholds=None):
     """``segment()`` up to and including the mask assembly, with the result left where it was made: the float32 0 / 1 stack
     [n, output_size[0], output_size[1], 4] on the device (channel = CLASS_ID - 1; classes that were not asked for stay 0).  What
     ``postprocess.save_results`` / ``render_results`` take; ``segment()`` copies it to the host arrays of the reference's interface.
-    ``images``: the list of PIL images, or a uint8 CUDA tensor [n, H, W, 3] of RGB frames, which takes the device-preprocess path as it is."""
+    ``images``: the list of PIL images, or a uint8 CUDA tensor [n, H, W, 3] of RGB frames, which takes the device-preprocess path as it is.
+    ``thresholds`` (default ``None``: nothing changes): ``{class name: t}``; the logits channel of each class named is shifted by
+    ``curves.apply_thresholds`` before the assembly, so that its mask is cut at ``t`` instead of 0.5."""
     from . import _lib as L
+    if thresholds is not None:
+        from .curves import apply_thresholds, read_thresholds
+        thresholds = read_thresholds(thresholds)
     frames_u8 = None
     if torch.is_tensor(images):     # frames that are on the device already (pullback.normalize_volume / resize_pil_u8): nothing to upload
         if not (images.is_cuda and images.dtype == torch.uint8 and images.dim() == 4 and images.shape[3] == 3 and images.shape[0] > 0):
@@ -206,6 +211,8 @@ def segment_stack(images, output_size, classes, models_dir, device='cuda', batch
             tables[key] = (torch.from_numpy(cv2_nearest_index(z.shape[2], oh)).to(device),
                            torch.from_numpy(cv2_nearest_index(z.shape[3], ow)).to(device))
         rows, cols = tables[key]
+        if thresholds is not None and class_name in thresholds:
+            apply_thresholds(z, [int(ch)], [thresholds.pop(class_name)])      # (popped: a class listed twice is shifted once)
         L.check(L.lib().octseg_mask_assemble(L.ptr(z), n, z.shape[1], z.shape[2], z.shape[3], int(ch), L.ptr(stack), oh, ow, 4,
                                              CLASS_IDS[class_name] - 1, L.ptr(rows), L.ptr(cols), L.stream_ptr()))
     return stack
@@ -323,6 +330,15 @@ def _vote_keys(cfg):
     return folds, tta, mode
 
 
+def _threshold_key(cfg):
+    """The ``thresholds`` key (absent by default): the path of a ``curves.json`` or ``{class name: t}``, as ``{class name: t}`` or ``None``.  Unknown
+    class names and ``t`` outside (0, 1) are refused here, before anything is loaded."""
+    if cfg.get('thresholds') is None:
+        return None
+    from .curves import read_thresholds
+    return read_thresholds(cfg['thresholds'])
+
+
 def _save_vote(voted, paths, names, classes, save_dir):
     """A voted prediction's own files: ``{save_dir}/vote.json`` (``vote.vote_report``, slices in sorted file-name order, as ``analysis`` uses) and,
     where the dissent maps were asked for, ``{name}_dissent.png`` per frame (``vote.dissent_images``)."""
@@ -361,6 +377,9 @@ def main(argv=None):
     ``folds`` true or a ``tta`` the stack is voted by every ``fold_<k>`` network of a class on every view (``vote.segment_stack_voted``) and
     ``{save_dir}/vote.json`` (``vote.vote_report``) is written, slices in the order ``analysis`` uses; ``dissent_maps`` (default false) adds
     ``{name}_dissent.png`` per frame, grayscale, the maximum over the classes of ``dissent * (255 // members)``;
+    ``thresholds`` (absent by default): the path of a ``curves.json`` written by ``python -m oct_segmentation_amd.curves`` or a dict
+    ``{"Lumen": 0.4, ...}``: the masks of the classes named are cut at that probability instead of 0.5 (``curves.apply_thresholds`` on the
+    logits before the assembly, voted or not); unknown class names and values outside (0, 1) are refused before anything is loaded;
     ``device_resize`` (default true): ``RGB`` and ``L`` files go up at source size and ``data_processing``'s ``Image.resize`` runs on the GPU
     (``pullback.resize_pil_u8``, byte-identical; false restores the host resize for every file).  A ``data_dir`` that is a ``.npy`` file is a
     raw volume (a DICOM's ``pixel_array``) and goes through ``pullback.analyze_pullback``: see ``_main_volume``."""
@@ -373,6 +392,7 @@ def main(argv=None):
     if not logging.getLogger().handlers:
         logging.basicConfig(level=logging.INFO, format='[%(asctime)s][%(name)s][%(levelname)s] - %(message)s')
     cfg = load_config('predict', list(sys.argv[1:] if argv is None else argv))
+    thresholds = _threshold_key(cfg)
     device = 'cuda' if cfg.get('device', 'auto') in ('auto', 'gpu', 'cuda') else cfg['device']
     if not (str(device).startswith('cuda') and torch.cuda.is_available()):
         raise RuntimeError(f'predict needs a GPU (device={cfg.get("device")!r}): there is no CPU path')
@@ -383,6 +403,8 @@ def main(argv=None):
         raise FileNotFoundError(f'no images under {cfg["data_dir"]}')
     os.makedirs(str(cfg['save_dir']), exist_ok=True)
     if str(cfg['data_dir']).endswith('.npy'):
+        if thresholds is not None:      # analyze_pullback segments at 0.5: refuse, do not quietly serve the default cut
+            raise ValueError('thresholds apply to image files only: a .npy volume goes through pullback.analyze_pullback, which cuts at 0.5')
         _main_volume(cfg, device, dtypes, log)
         log.info(f'Overall computation time: {time.time() - start:.1f} s')
         log.info('Complete')
@@ -402,12 +424,12 @@ def main(argv=None):
         from .vote import segment_stack_voted
         voted = segment_stack_voted(images, cfg['output_size'], cfg['classes'], str(cfg['models_dir']), tta=tta, folds=folds, mode=vote_mode,
                                     want_dissent=bool(cfg.get('dissent_maps', False)), device=device, batch_size=int(cfg.get('batch_size', 8)),
-                                    compute_dtype=dtypes[str(cfg.get('compute_dtype', 'bf16'))])
+                                    compute_dtype=dtypes[str(cfg.get('compute_dtype', 'bf16'))], thresholds=thresholds)
         stack = voted.stack
     else:
         stack = segment_stack(images, cfg['output_size'], cfg['classes'], str(cfg['models_dir']), device=device,
                               batch_size=int(cfg.get('batch_size', 8)), compute_dtype=dtypes[str(cfg.get('compute_dtype', 'bf16'))],
-                              use_graph=bool(cfg.get('use_graph', False)), device_preprocess=True)
+                              use_graph=bool(cfg.get('use_graph', False)), device_preprocess=True, thresholds=thresholds)
     if voted is not None:
         _save_vote(voted, paths, names, cfg['classes'], str(cfg['save_dir']))
     if bool(cfg.get('clean', False)):

@@ -142,20 +142,25 @@ def find_members(models_dir, class_name):
 
 
 def segment_stack_voted(images, output_size, classes, models_dir, tta='none', folds=True, mode='soft', want_prob=False, want_dissent=False,
-                        device='cuda', batch_size=8, compute_dtype=torch.bfloat16):
+                        device='cuda', batch_size=8, compute_dtype=torch.bfloat16, thresholds=None):
     """``predict.segment_stack`` voted: per class every fold found by ``find_members`` (``folds=False``: the single directory of today) runs once per
     view of ``VIEW_SETS[tta]``, and the ``M = folds x views`` logits tensors of a batch (folds outer, views inner) go into one
     ``octseg_vote_assemble`` launch per class.  Preprocessing, channel mapping and resize tables are ``segment_stack``'s (device-preprocess path);
     a two-class FC_LC network runs once and is voted twice.  Eager forwards; one batch of member logits is alive at a time.
     Returns ``VoteResult(stack, prob, dissent, stats, members)``: ``stack`` float32 [n, H, W, 4] as ``segment_stack``'s, ``prob`` float32 and
     ``dissent`` uint8 of the same shape (``None`` unless asked for), ``stats`` int32 [n, 4, 4] (frame, CLASS_ID - 1, STAT_COLUMNS), ``members``
-    class name -> M.  Channels of classes that were not asked for stay 0."""
+    class name -> M.  Channels of classes that were not asked for stay 0.  ``thresholds`` (default ``None``: nothing changes): ``{class name: t}``;
+    every member's logits channel of a class named is shifted by ``curves.apply_thresholds`` before the vote, so that each member votes, and the
+    soft vote cuts, at ``t`` instead of 0.5."""
     from .model import CLASS_IDS
     from .predict import MODELS_META, _resize_frames_on_device, _upload_frames_u8, cv2_nearest_index, load_model
     if tta not in VIEW_SETS:
         raise ValueError(f'tta must be one of {sorted(VIEW_SETS)}, got {tta!r}')
     if mode not in MODES:
         raise ValueError(f"mode must be 'soft' or 'majority', got {mode!r}")
+    if thresholds is not None:
+        from .curves import apply_thresholds, read_thresholds
+        thresholds = read_thresholds(thresholds)
     if torch.is_tensor(images):
         if not (images.is_cuda and images.dtype == torch.uint8 and images.dim() == 4 and images.shape[3] == 3 and images.shape[0] > 0):
             raise ValueError('a frame tensor must be a non-empty uint8 CUDA tensor [n, H, W, 3] (RGB)')
@@ -195,12 +200,18 @@ def segment_stack_voted(images, output_size, classes, models_dir, tta='none', fo
             if size not in tables:   # cv2.resize(predict_mask, tuple(output_size), INTER_NEAREST): resizeNN's row / column tables
                 tables[size] = (torch.from_numpy(cv2_nearest_index(size, oh)).to(device), torch.from_numpy(cv2_nearest_index(size, ow)).to(device))
             rows, cols = tables[size]
+            shifted = set()      # (a class listed twice is shifted once per batch)
             for class_name in classes:
                 meta = MODELS_META[class_name]
                 if meta['model_dir'] != key:
                     continue
                 c = CLASS_IDS[class_name] - 1
-                vote_logits(logits, [meta['index'] if z.shape[1] > 1 else 0 for z in logits], codes, stack[i:i + b], c, rows, cols, mode,
+                chans = [meta['index'] if z.shape[1] > 1 else 0 for z in logits]
+                if thresholds is not None and class_name in thresholds and class_name not in shifted:
+                    for z, ch in zip(logits, chans):
+                        apply_thresholds(z, [ch], [thresholds[class_name]])
+                    shifted.add(class_name)
+                vote_logits(logits, chans, codes, stack[i:i + b], c, rows, cols, mode,
                             prob=None if prob is None else prob[i:i + b], dissent=None if dissent is None else dissent[i:i + b],
                             stats=stats[c, i:i + b])
             del logits, xs, x
