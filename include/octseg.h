@@ -44,6 +44,9 @@
  *   octseg_stack_polar / octseg_frames_unwrap
  *                                      (no reference counterpart) the rays of calculate_object_thickness walked to their end: first entry, first
  *                                      exit, last set step, set steps and runs per slice, class and degree; the polar label map and frame view
+ *   octseg_stack_moments / octseg_moment_origins / octseg_stack_polar_at
+ *                                      (no reference counterpart) raw moments to second order, bounding box and crack perimeter of every mask
+ *                                      plane; its centroid as a pixel; the polar profile walked from that pixel: lumen area and diameters
  *   octseg_stack_components / octseg_stack_cleanup / octseg_components_scratch_bytes
  *                                      MaskProcessor.smooth_mask / .remove_artifacts, which process_pair runs over every annotated object
  *                                      (src/data/mask_processor.py:5-37, src/data/convert_int_to_cv.py:191-199)
@@ -391,6 +394,52 @@ int octseg_stack_polar(const float* stack, int N, int H, int W, int stack_channe
                        int* prof, unsigned char* map /* may be NULL */, void* stream);
 int octseg_frames_unwrap(const unsigned char* frames, int N, int H, int W, int channels, const int* ray_pix, const int* ray_len, int R,
                          unsigned char* out, void* stream);
+
+/* Lumen geometry (no reference counterpart; DESIGN.md section 5m, pinned to tests/shape_ref.py).  octseg_stack_measure and octseg_stack_polar
+ * walk from the frame centre (W / 2, H / 2); the catheter is rarely at the lumen's centre, and a ray from the frame centre through a lumen does
+ * not measure a lumen diameter.  The reference's own thickness is taken from the object's centroid (calculate_thickness_contour,
+ * src/app/tools/analysis.py:21-57), but along cv2.findContours' traversal, which nothing here can pin: the three calls below are the nearest
+ * independently definable thing -- moments, the centroid as a pixel, and the same five integers per ray from that pixel -- and are NOT that
+ * function.  stack: device f32 [N][H][W][channels], any value != 0 is set; a plane is one (slice, channel) pair.
+ *
+ * octseg_stack_moments: mom int64 [N][channels][OCTSEG_MOMENT_FIELDS], 8-byte aligned, over the set pixels (x, y) of the plane, x the column:
+ *    0 M00  sum of 1        3 M20  sum of x * x      6 XMIN  smallest x; W on an empty plane     10 EDGES  the crack perimeter: the number of
+ *    1 M10  sum of x        4 M11  sum of x * y      7 XMAX  largest x; -1 on an empty plane               (set pixel, 4-neighbour) pairs whose
+ *    2 M01  sum of y        5 M02  sum of y * y      8 YMIN  smallest y; H on an empty plane               neighbour is clear or outside the frame
+ *                                                    9 YMAX  largest y; -1 on an empty plane     11        0
+ * The call initialises mom on the stream (one launch), then makes one streaming pass over the stack (one launch; float4 loads for 4 channels on
+ * a 16-byte aligned base, dword loads otherwise).  Everything is integer, so the result does not depend on the order of the additions and
+ * EQUALS the restatement.  Bounds: channels <= 16, H <= OCTSEG_SHAPE_MAX_EXTENT, W <= OCTSEG_SHAPE_MAX_EXTENT, H * W < 2^31: a plane has fewer
+ * than 2^31 pixels and each adds less than 2^30 to a second moment, so every field stays below 2^61 and well inside an int64.
+ *
+ * octseg_moment_origins: origins int32 [N][channels][3] = x, y, AT.  With M = the moments of the plane itself (ref_channel < 0) or of channel
+ * ref_channel of the same slice (then every channel of a slice gets the same x, y): x = (2 * M10 + M00) / (2 * M00), y = (2 * M01 + M00) /
+ * (2 * M00) in integer arithmetic -- the centroid rounded to the nearest pixel, halves up; AT = 1 iff THIS channel is set at (x, y) (a ring's
+ * centroid is not on the ring).  M00 == 0: (-1, -1, 0).  mom is what octseg_stack_moments wrote for the same stack.  One launch of one thread
+ * per plane, no host synchronisation; ref_channel >= channels is refused.
+ *
+ * octseg_stack_polar_at: prof int32 [N][channels][360][5] = IN, OUT, LAST, HITS, RUNS exactly as octseg_stack_polar defines them, and
+ * len int32 [N][channels][360], over the steps r = 1 .. len of
+ *   pixel(r) = (origins[n][c][0] + ray_off[angle][r - 1][0], origins[n][c][1] + ray_off[angle][r - 1][1])      (x, y; origins' third entry is not read)
+ *   ray_off: device int32 [360][R][2], made by the host as (floor(r * cos(radians(angle)) + 0.5), floor(r * sin(radians(angle)) + 0.5)) in
+ *            CPython's double arithmetic for r = 1 .. R: the NEAREST pixel.  The reference's int(cx + r * cos) truncates the sum, so its step
+ *            pattern depends on the centre it is added to and cannot be a table of offsets; this is a stated deviation.  May be null when R == 0.
+ * A ray ends at its first step outside the frame (or after R steps): len is the number of steps inside, and OUT == len means the frame (or the
+ * table) cut the first run.  An origin outside [0, W) x [0, H) -- the (-1, -1) of an empty plane -- gives a zero profile and len 0.  The device
+ * does no trigonometry, adds in 64 bits and gathers only pixels inside the frame: a wrong table gives wrong samples, never a stray read.
+ * channels <= 8, as octseg_stack_polar.  Where all channels of a slice share an origin one gather serves them all.  One launch.
+ *
+ * Integer results, no tolerance.  The host mirror (oct_segmentation_amd/shape.py) makes the table and turns the integers into the shape table and
+ * the lumen report.  Enqueue only.  Null pointer (ray_off may be null only with R == 0), N, H, W, channels <= 0, channels > 16 (8 for
+ * octseg_stack_polar_at), H or W > OCTSEG_SHAPE_MAX_EXTENT, H * W >= 2^31, mom not 8-byte aligned, ref_channel >= channels, R < 0:
+ * OCTSEG_BAD_ARG.  Nothing is launched and no output is touched then. */
+#define OCTSEG_MOMENT_FIELDS 12
+#define OCTSEG_SHAPE_MAX_EXTENT 32768
+int octseg_stack_moments(const float* stack, int N, int H, int W, int channels, long long* mom, void* stream);
+int octseg_moment_origins(const float* stack, const long long* mom, int N, int H, int W, int channels, int ref_channel /* < 0: own */,
+                          int* origins, void* stream);
+int octseg_stack_polar_at(const float* stack, int N, int H, int W, int channels, const int* origins, const int* ray_off, int R, int* prof,
+                          int* len, void* stream);
 
 /* Mask clean-up (reference src/data/mask_processor.py:5-37: MaskProcessor.smooth_mask and .remove_artifacts, run by process_pair,
  * src/data/convert_int_to_cv.py:191-199), on connected components by pixel count (DESIGN.md section 5g states how that differs from

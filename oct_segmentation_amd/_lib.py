@@ -146,6 +146,11 @@ SYMBOLS = {
     # float32 mask stack + the same ray table -> int32 polar profile [N, C, 360, 5] (+ uint8 label map); uint8 frames -> polar view (csrc/polar.hip)
     'octseg_stack_polar': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P]),
     'octseg_frames_unwrap': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P]),
+    # float32 mask stack -> int64 moments, box and crack perimeter [N, C, 12]; -> int32 centroid pixels [N, C, 3]; + offset table [360, R, 2] ->
+    # the polar profile from those pixels and the rays' lengths (csrc/shape.hip)
+    'octseg_stack_moments': (C.c_int, [_P] + [C.c_int] * 4 + [_P, _P]),
+    'octseg_moment_origins': (C.c_int, [_P, _P] + [C.c_int] * 5 + [_P, _P]),
+    'octseg_stack_polar_at': (C.c_int, [_P] + [C.c_int] * 4 + [_P, _P, C.c_int, _P, _P, _P]),
     # float32 mask stack -> connected components (labels, count, the 8 largest) and the cleaned stack: smooth, keep-largest, hole fill
     # (csrc/components.hip)
     'octseg_components_scratch_bytes': (C.c_size_t, [C.c_int] * 3),

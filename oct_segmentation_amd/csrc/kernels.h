@@ -376,6 +376,19 @@ hipError_t launch_stack_polar(const float* stack, int N, int H, int W, int SC, c
 hipError_t launch_frames_unwrap(const uint8_t* frames, int N, int H, int W, int C, const int* ray_pix, const int* ray_len, int R, uint8_t* out,
                                 hipStream_t st);
 
+// lumen geometry (shape.hip): launch_stack_moments -- int64 [N][SC][12] raw moments to second order, bounding box and crack perimeter of every
+// plane; one initialising launch, then one streaming pass.  launch_moment_origins -- int32 [N][SC][3] = the centroid rounded to a pixel and whether
+// the plane is set there, from the plane's own moments (ref_channel < 0) or from channel ref_channel of the slice; one tiny launch.
+// launch_stack_polar_at -- polar.hip's five integers per slice, channel (at most 8) and degree from origins[n][c] along ray_off [360][R][2], and
+// the number of steps inside the frame; one launch
+constexpr int SHAPE_MOMENT_FIELDS = 12;
+constexpr int SHAPE_MAX_EXTENT = 32768;                     // H, W <= 2^15 and H * W < 2^31: every sum stays below 2^60
+hipError_t launch_stack_moments(const float* stack, int N, int H, int W, int SC, long long* mom, hipStream_t st);
+hipError_t launch_moment_origins(const float* stack, const long long* mom, int N, int H, int W, int SC, int ref_channel, int* origins,
+                                 hipStream_t st);
+hipError_t launch_stack_polar_at(const float* stack, int N, int H, int W, int SC, const int* origins, const int* ray_off, int R, int* prof,
+                                 int* length, hipStream_t st);
+
 // mask clean-up (components.hip): connected components of every (slice, channel) plane by union-find on bit planes, the 8 largest with their
 // bounding boxes, keep-largest / min-area filter, hole fill (the same labelling on the complement, 4-connected) and the reference's
 // smooth_mask chain.  scratch: components_scratch_bytes(N * C, H, W) device bytes; labels / ncomp / top are optional (null = skipped)

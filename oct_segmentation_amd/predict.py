@@ -288,7 +288,7 @@ def _main_volume(cfg, device, dtypes, log):
     res = analyze_pullback(volume, str(cfg['models_dir']), cfg['classes'], output_size=cfg['output_size'], names=names, render=True,
                            close_iterations=int(cfg.get('close_iterations', 1)), device=device, batch_size=int(cfg.get('batch_size', 8)),
                            compute_dtype=dtypes[str(cfg.get('compute_dtype', 'bf16'))], use_graph=bool(cfg.get('use_graph', False)),
-                           clean=bool(cfg.get('clean', False)), plaque=bool(cfg.get('plaque', False)))
+                           clean=bool(cfg.get('clean', False)), plaque=bool(cfg.get('plaque', False)), lumen=bool(cfg.get('lumen', False)))
     out = torch.stack([res.overlay, res.color_mask]).cpu().numpy()
     save_dir = str(cfg['save_dir'])
     for i, name in enumerate(names):
@@ -301,6 +301,14 @@ def _main_volume(cfg, device, dtypes, log):
         _save_plaque(res.plaque, res.stack, cfg['classes'], save_dir)
     if bool(cfg.get('lesions', False)):
         _save_lesions(res.stack, names, save_dir)
+    if res.lumen is not None:
+        _save_lumen(res.lumen, save_dir)
+
+
+def _save_lumen(report, save_dir):
+    """``lumen=true``: ``{save_dir}/lumen.json``, ``shape.lumen_report`` of the stack that is rendered and measured (after ``clean``)."""
+    with open(os.path.join(save_dir, 'lumen.json'), 'w') as f:
+        json.dump(report, f)
 
 
 def _save_lesions(stack, names, save_dir):
@@ -373,6 +381,9 @@ def main(argv=None):
     arc, cap thickness where lipid lies behind it), and ``plaque_carpet.png`` (``polar.carpet_view``), slices in the order ``analysis`` uses;
     ``lesions`` (default false): also write ``{save_dir}/lesions.json``, the 3-D lesion report of the same stack (``lesions.lesion_report``:
     components across the slices, their length, voxels, bounding box and area profile), slices in the order ``analysis`` uses;
+    ``lumen`` (default false): also write ``{save_dir}/lumen.json``, the lumen report of the same stack (``shape.lumen_report``: lumen area and
+    the diameters through the lumen's own centroid per frame, the minimal-lumen-area frame, percent area stenosis), slices in the order
+    ``analysis`` uses;
     ``folds`` (default false), ``tta`` (``none`` | ``flips`` | ``d4``, default ``none``), ``vote`` (``soft`` | ``majority``, default ``soft``): with
     ``folds`` true or a ``tta`` the stack is voted by every ``fold_<k>`` network of a class on every view (``vote.segment_stack_voted``) and
     ``{save_dir}/vote.json`` (``vote.vote_report``) is written, slices in the order ``analysis`` uses; ``dissent_maps`` (default false) adds
@@ -452,6 +463,10 @@ def main(argv=None):
     if bool(cfg.get('lesions', False)):
         order = sorted(range(len(paths)), key=lambda i: os.path.basename(paths[i]))
         _save_lesions(stack[torch.tensor(order, device=stack.device)], [names[i] for i in order], str(cfg['save_dir']))
+    if bool(cfg.get('lumen', False)):
+        from .shape import lumen_report
+        order = sorted(range(len(paths)), key=lambda i: os.path.basename(paths[i]))
+        _save_lumen(lumen_report(stack[torch.tensor(order, device=stack.device)], [names[i] for i in order]), str(cfg['save_dir']))
     log.info(f'Overall computation time: {time.time() - start:.1f} s')
     log.info('Complete')
     return 0

@@ -27,7 +27,7 @@ BICUBIC_SUPPORT = 2.0
 
 _tables = {}   # (in, out, device) -> (bounds, kk, ksize) device int32 tensors
 
-Pullback = namedtuple('Pullback', 'data stack frames overlay color_mask plaque', defaults=(None,))
+Pullback = namedtuple('Pullback', 'data stack frames overlay color_mask plaque lumen', defaults=(None, None))
 
 
 def _bicubic(x):
@@ -158,7 +158,7 @@ def normalize_volume(volume, swap_rb=True, device='cuda', return_minmax=False):
 
 
 def analyze_pullback(volume, models_dir, classes, output_size=(1000, 1000), names=None, render=False, swap_rb=True, close_iterations=1,
-                     clean=None, plaque=None, **segment_kwargs):
+                     clean=None, plaque=None, lumen=None, **segment_kwargs):
     """From a raw volume to the app's dict in one call: ``normalize_volume`` -> ``resize_pil_u8`` -> ``predict.segment_stack`` ->
     ``analysis.analyze_stack``; with ``render=True`` also ``postprocess.render_results``.  The frames go up once, at source size, and nothing
     comes back but the results.
@@ -171,9 +171,12 @@ def analyze_pullback(volume, models_dir, classes, output_size=(1000, 1000), name
     keywords: the mask stack is cleaned once (smoothing, keep-largest, hole fill) and the cleaned stack is measured, rendered and returned.
     ``plaque``: None (default), True or a dict of ``polar.plaque_report`` keywords (``cap``, ``lipid``, ``thin_cap``, ``wide_arc``, ``ratio``):
     the polar plaque report of the stack that is measured (after ``clean``), with the same names and, unless given, the same ``ratio``.
+    ``lumen``: None (default), True or a dict of ``shape.lumen_report`` keywords (``lumen``, ``ref_window``, ``ratio``): the lumen report of the
+    same stack, with the same names and, unless given, the same ``ratio``.
 
-    Returns ``Pullback(data, stack, frames, overlay, color_mask, plaque)``: the dict, the float32 mask stack and the uint8 RGB frames at
-    output size on the device; overlay and colour mask (uint8 CUDA [S,oh,ow,3]) with ``render=True``, else None; ``plaque`` the report or None."""
+    Returns ``Pullback(data, stack, frames, overlay, color_mask, plaque, lumen)``: the dict, the float32 mask stack and the uint8 RGB frames at
+    output size on the device; overlay and colour mask (uint8 CUDA [S,oh,ow,3]) with ``render=True``, else None; ``plaque`` and ``lumen`` the
+    reports or None."""
     from .analysis import analyze_stack
     from .postprocess import render_results
     from .predict import segment_stack
@@ -185,6 +188,14 @@ def analyze_pullback(volume, models_dir, classes, output_size=(1000, 1000), name
         bad = set(pk) - {'ratio', 'cap', 'lipid', 'thin_cap', 'wide_arc'}
         if bad:
             raise ValueError(f'unknown plaque_report keywords: {sorted(bad)}')
+    lk = None
+    if lumen is not None and lumen is not False:
+        if lumen is not True and not isinstance(lumen, dict):
+            raise ValueError(f'lumen must be None, a bool or a dict of lumen_report keywords, got {lumen!r}')
+        lk = {} if lumen is True else dict(lumen)
+        bad = set(lk) - {'ratio', 'lumen', 'ref_window'}
+        if bad:
+            raise ValueError(f'unknown lumen_report keywords: {sorted(bad)}')
     frames = normalize_volume(volume, swap_rb=swap_rb, device=segment_kwargs.get('device', 'cuda'))
     S, H = int(frames.shape[0]), int(frames.shape[1])
     frames = resize_pil_u8(frames, (int(output_size[1]), int(output_size[0])))       # PIL sizes are (width, height)
@@ -204,4 +215,9 @@ def analyze_pullback(volume, models_dir, classes, output_size=(1000, 1000), name
         from .polar import plaque_report
         pk.setdefault('ratio', int(H * 150 // 1000))
         report = plaque_report(stack, names, **pk)
-    return Pullback(data, stack, frames, overlay, color_mask, report)
+    lumen_rep = None
+    if lk is not None:
+        from .shape import lumen_report
+        lk.setdefault('ratio', int(H * 150 // 1000))
+        lumen_rep = lumen_report(stack, names, **lk)
+    return Pullback(data, stack, frames, overlay, color_mask, report, lumen_rep)
