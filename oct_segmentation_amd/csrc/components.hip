@@ -2,65 +2,42 @@
 // annotated object (convert_int_to_cv.py:191-199): smooth_mask (open, close, dilate with a frame-sized ellipse) and remove_artifacts (keep the
 // largest blobs, filled), restated on connected components by PIXEL COUNT (DESIGN.md section 5g states the deviation from cv2.contourArea).
 //
-// A plane is one (slice, channel) pair of the float32 stack [N][H][W][C].  Every plane lives as a BIT PLANE in scratch: row y is W64 = ceil(W / 64)
-// 64-bit words, bit i of word j = pixel 64 j + i, bits past the frame always 0 (1 bit per pixel instead of the stack's 4 bytes; an all-zero word
-// is the early exit of every kernel below, so an empty plane costs its word reads and nothing else).  Every phase that needs a grid-wide order
-// is a launch of its own on the caller's stream; no workgroup ever waits on another, there is no flag, no spin and no cooperative launch.
+// A plane is one (slice, channel) pair of the float32 stack [N][H][W][C] and lives as a bit plane in scratch (bitplanes.h: the layout, and the
+// geometry "S sets of D planes" this file uses with S = N * C, D = 1, so parent and area hold pixel indices y * W + x).  An all-zero word is the
+// early exit of every kernel, so an empty plane costs its word reads and nothing else.  Every phase that needs a grid-wide order is a launch of
+// its own on the caller's stream; no workgroup ever waits on another, there is no flag, no spin and no cooperative launch.
 //
-//   pack        stack -> bits: a wave takes 64 pixels of a row, `v != 0` per channel is a ballot = one word (the 16 B / pixel stack is read once)
+// pack / unpack, the labelling (init, merge, flatten, labels; its termination argument) and keep are the shared kernels of bitplanes.hip.  Here:
+//
 //   morph       one smoothing stage: the row-word technique of render.hip on global words.  A structuring-element row of columns lo..hi is the
 //               OR (dilate) / AND (erode) of the word shifted by lo..hi, neighbours' bits shifted in; outside the frame the source reads as the
 //               stage's neutral value (OpenCV: "outside does not take part").  Element applied as given (not reflected), anchor k / 2.
-//   init        parent[p] = first pixel of p's horizontal run inside its word: runs need no atomics.  parent holds pixel indices y * W + x.
-//   merge       union-find, label equivalence: a set pixel unites with its left neighbour across a word border and with the row above; run
-//               structure makes most pixels skip (only the first pixel of an overlap unites).  8-connected adds the two upper diagonals.
-//   flatten     parent[run start] = root(run start); the other pixels of a run keep pointing at their run start, so every pixel is two hops
-//               from its root and only one pixel per run walks a chain.  The root is the component's smallest index = its first pixel in
-//               raster order: label = 1 + root.
 //   area        a thread per word adds run lengths to area[root] with integer atomics; a run that starts at its own root appends the root to
 //               the plane's component list.
 //   select      ONE workgroup per plane: ncomp, the 8 largest by (area descending, first pixel ascending), the k-th largest area, the threshold.
 //   bbox        runs of the table's components reduce their inclusive bounding box with atomicMin / atomicMax.
-//   keep        kept bits = runs whose component has area >= threshold.
-//   hole fill   THE SAME init / merge / flatten on the complement inside the frame with 4-connectivity; `border` marks the roots of background
-//               components that reach the frame border (the outside of the frame as one component), `fill` sets the runs of all others.
-//   unpack      bits -> float32 0.0 / 1.0 in the stack's layout;   labels: parent -> int32 [plane][H][W], background 0.
-//
-// TERMINATION of every union-find loop: parent[x] <= x always (init writes a run start, atomicMin only lowers a value), a non-root has
-// parent[x] < x, so a find walks strictly downwards and ends after at most H * W steps; a unite either links a root (done) or continues with a
-// strictly smaller pair.  Labels only ever decrease.  A stale read of parent (another CU's L1) yields an older, larger ancestor of the same
-// set: the walk still descends, and the atomicMin that links returns the true value, so a lost race is seen and repeated, never missed.
+//   hole fill   THE SAME labelling on the complement inside the frame with 4-connectivity; `border` marks the roots of background components
+//               that reach the frame border (the outside of the frame as one component), `fill` sets the runs of all others.
 #include <algorithm>
 #include <cmath>
 
-#include "common.h"
+#include "bitplanes.h"
 #include "kernels.h"
-#include "unionfind.h"   // u64, inmask, ctz64, runlen, runmask, find_root, unite
 
 namespace octseg {
 
 namespace {
 
-constexpr int NT = 256, WAVES = NT / 64;
 #ifndef OCTSEG_SEL_NT
 #define OCTSEG_SEL_NT 256
 #endif
 constexpr int SEL_NT = OCTSEG_SEL_NT;     // workgroup of select_kernel (any power of two)
 constexpr int TOPK = 8, TCOL = 6;
-constexpr unsigned MAX_GRID = 1u << 20;
-
-struct Geo { int H, W, W64, HW; };
 
 struct Elem { int k, a; int lo[7], hi[7]; };   // cv2.getStructuringElement(MORPH_ELLIPSE, (k, k)): row i is set on columns lo[i]..hi[i]; anchor a
 
-// word j of row y as the labelling sees it: 0 outside the frame; inv = the complement inside the frame
-__device__ __forceinline__ u64 rdw(const u64* __restrict__ plane, int y, int j, const Geo& g, int inv) {
-  if (y < 0 || y >= g.H || j < 0 || j >= g.W64) return 0ull;
-  const u64 w = plane[(size_t)y * g.W64 + j];
-  return inv ? ~w & inmask(j, g.W) : w;
-}
 // word j of row y as a morphology stage sees it: outside the frame = the neutral value (0 dilate, 1 erode)
-__device__ __forceinline__ u64 rdm(const u64* __restrict__ plane, int y, int j, const Geo& g, int ero) {
+__device__ __forceinline__ u64 rdm(const u64* __restrict__ plane, int y, int j, const BitGeo& g, int ero) {
   if (y < 0 || y >= g.H || j < 0 || j >= g.W64) return ero ? ~0ull : 0ull;
   const u64 w = plane[(size_t)y * g.W64 + j];
   return ero ? w | ~inmask(j, g.W) : w;
@@ -68,53 +45,8 @@ __device__ __forceinline__ u64 rdm(const u64* __restrict__ plane, int y, int j, 
 
 }  // namespace
 
-// ---- stack <-> bit planes
-__global__ __launch_bounds__(NT) void pack_kernel(const float* __restrict__ stack, int N, Geo g, int C, u64* __restrict__ bits, int vec) {
-  const int lane = threadIdx.x & 63;
-  const size_t nw = (size_t)gridDim.x * WAVES, total = (size_t)N * g.H * g.W64;
-  for (size_t it = (size_t)blockIdx.x * WAVES + (threadIdx.x >> 6); it < total; it += nw) {     // wave-uniform
-    const int j = (int)(it % g.W64), y = (int)((it / g.W64) % g.H);
-    const size_t n = it / ((size_t)g.W64 * g.H);
-    const int x = j * 64 + lane;
-    const bool ok = x < g.W;
-    const float* px = stack + ((n * g.H + y) * (size_t)g.W + (ok ? x : g.W - 1)) * C;
-    if (vec) {
-      const float4 v = *(const float4*)px;
-      const u64 w0 = __ballot(ok && v.x != 0.f), w1 = __ballot(ok && v.y != 0.f), w2 = __ballot(ok && v.z != 0.f), w3 = __ballot(ok && v.w != 0.f);
-      if (lane < 4) bits[((n * 4 + lane) * g.H + y) * (size_t)g.W64 + j] = lane == 0 ? w0 : lane == 1 ? w1 : lane == 2 ? w2 : w3;
-    } else {
-      for (int c = 0; c < C; ++c) {
-        const u64 w = __ballot(ok && px[c] != 0.f);
-        if (lane == 0) bits[((n * C + c) * g.H + y) * (size_t)g.W64 + j] = w;
-      }
-    }
-  }
-}
-
-__global__ __launch_bounds__(NT) void unpack_kernel(const u64* __restrict__ bits, int N, Geo g, int C, float* __restrict__ out, int vec) {
-  const int lane = threadIdx.x & 63;
-  const size_t nw = (size_t)gridDim.x * WAVES, total = (size_t)N * g.H * g.W64;
-  for (size_t it = (size_t)blockIdx.x * WAVES + (threadIdx.x >> 6); it < total; it += nw) {
-    const int j = (int)(it % g.W64), y = (int)((it / g.W64) % g.H);
-    const size_t n = it / ((size_t)g.W64 * g.H);
-    const int x = j * 64 + lane;
-    if (x >= g.W) continue;
-    float* px = out + ((n * g.H + y) * (size_t)g.W + x) * C;
-    if (vec) {
-      float4 v;
-      v.x = (float)((bits[((n * 4 + 0) * g.H + y) * (size_t)g.W64 + j] >> lane) & 1ull);
-      v.y = (float)((bits[((n * 4 + 1) * g.H + y) * (size_t)g.W64 + j] >> lane) & 1ull);
-      v.z = (float)((bits[((n * 4 + 2) * g.H + y) * (size_t)g.W64 + j] >> lane) & 1ull);
-      v.w = (float)((bits[((n * 4 + 3) * g.H + y) * (size_t)g.W64 + j] >> lane) & 1ull);
-      *(float4*)px = v;
-    } else {
-      for (int c = 0; c < C; ++c) px[c] = (float)((bits[((n * C + c) * g.H + y) * (size_t)g.W64 + j] >> lane) & 1ull);
-    }
-  }
-}
-
 // ---- one smoothing stage, a thread per word
-__global__ __launch_bounds__(NT) void morph_kernel(const u64* __restrict__ src, u64* __restrict__ dst, int P, Geo g, Elem el, int ero) {
+__global__ __launch_bounds__(NT) void morph_kernel(const u64* __restrict__ src, u64* __restrict__ dst, int P, BitGeo g, Elem el, int ero) {
   const size_t total = (size_t)P * g.H * g.W64;
   for (size_t it = (size_t)blockIdx.x * NT + threadIdx.x; it < total; it += (size_t)gridDim.x * NT) {
     const int j = (int)(it % g.W64), y = (int)((it / g.W64) % g.H);
@@ -133,82 +65,10 @@ __global__ __launch_bounds__(NT) void morph_kernel(const u64* __restrict__ src, 
   }
 }
 
-// ---- labelling, a lane per pixel (a wave per word)
-__global__ __launch_bounds__(NT) void init_kernel(const u64* __restrict__ bits, int P, Geo g, int inv, int* __restrict__ parent, int* __restrict__ area) {
-  const int lane = threadIdx.x & 63;
-  const size_t nw = (size_t)gridDim.x * WAVES, total = (size_t)P * g.H * g.W64;
-  for (size_t it = (size_t)blockIdx.x * WAVES + (threadIdx.x >> 6); it < total; it += nw) {
-    const int j = (int)(it % g.W64), y = (int)((it / g.W64) % g.H);
-    const size_t pl = it / ((size_t)g.W64 * g.H);
-    const u64 c = rdw(bits + pl * g.H * g.W64, y, j, g, inv);
-    if (!c || !((c >> lane) & 1ull)) continue;                // bits past the frame are clear: x < W below
-    const u64 below = ~c & ((1ull << lane) - 1ull);           // clear bits under this lane
-    const int start = below ? 64 - __clzll((long long)below) : 0;
-    const int p = y * g.W + j * 64 + lane;
-    parent[pl * g.HW + p] = p - (lane - start);
-    area[pl * g.HW + p] = 0;
-  }
-}
-
-__global__ __launch_bounds__(NT) void merge_kernel(const u64* __restrict__ bits, int P, Geo g, int inv, int conn8, int* __restrict__ parent) {
-  const int lane = threadIdx.x & 63;
-  const size_t nw = (size_t)gridDim.x * WAVES, total = (size_t)P * g.H * g.W64;
-  for (size_t it = (size_t)blockIdx.x * WAVES + (threadIdx.x >> 6); it < total; it += nw) {
-    const int j = (int)(it % g.W64), y = (int)((it / g.W64) % g.H);
-    const size_t pl = it / ((size_t)g.W64 * g.H);
-    const u64* plane = bits + pl * g.H * g.W64;
-    const u64 c = rdw(plane, y, j, g, inv);
-    if (!c || !((c >> lane) & 1ull)) continue;
-    const u64 cl = rdw(plane, y, j - 1, g, inv), cr = rdw(plane, y, j + 1, g, inv);
-    const u64 u = rdw(plane, y - 1, j, g, inv), ul = rdw(plane, y - 1, j - 1, g, inv), ur = rdw(plane, y - 1, j + 1, g, inv);
-    const bool w = lane ? (c >> (lane - 1)) & 1ull : cl >> 63, e = lane < 63 ? (c >> (lane + 1)) & 1ull : cr & 1ull;
-    const bool n = (u >> lane) & 1ull, nwb = lane ? (u >> (lane - 1)) & 1ull : ul >> 63, neb = lane < 63 ? (u >> (lane + 1)) & 1ull : ur & 1ull;
-    int* par = parent + pl * g.HW;
-    const int p = y * g.W + j * 64 + lane;
-    if (lane == 0 && w) unite(par, p, p - 1);                           // runs were joined inside a word only
-    if (n && !(w && nwb)) unite(par, p, p - g.W);                       // with w and nw set the left neighbour unites with the row above
-    if (conn8 && !n) {
-      if (nwb && !w) unite(par, p, p - g.W - 1);                        // with w set, nw is w's upper neighbour
-      if (neb && !e) unite(par, p, p - g.W + 1);                        // with e set, ne is e's upper neighbour
-    }
-  }
-}
-
-__global__ __launch_bounds__(NT) void flatten_kernel(const u64* __restrict__ bits, int P, Geo g, int inv, int* __restrict__ parent) {
-  const int lane = threadIdx.x & 63;
-  const size_t nw = (size_t)gridDim.x * WAVES, total = (size_t)P * g.H * g.W64;
-  for (size_t it = (size_t)blockIdx.x * WAVES + (threadIdx.x >> 6); it < total; it += nw) {
-    const int j = (int)(it % g.W64), y = (int)((it / g.W64) % g.H);
-    const size_t pl = it / ((size_t)g.W64 * g.H);
-    const u64 c = rdw(bits + pl * g.H * g.W64, y, j, g, inv);
-    if (!c || !((c >> lane) & 1ull)) continue;
-    if (lane && ((c >> (lane - 1)) & 1ull)) continue;           // not a run start: its parent is the run start since init, one hop from the root
-    int* par = parent + pl * g.HW;
-    const int p = y * g.W + j * 64 + lane;
-    // the forest is final (merge_kernel has completed): every value a concurrent flatten writes is the root, a valid ancestor
-    const int r = find_root(par, p);
-    if (r != p) par[p] = r;
-  }
-}
-
-__global__ __launch_bounds__(NT) void labels_kernel(const u64* __restrict__ bits, int P, Geo g, const int* __restrict__ parent, int* __restrict__ labels) {
-  const int lane = threadIdx.x & 63;
-  const size_t nw = (size_t)gridDim.x * WAVES, total = (size_t)P * g.H * g.W64;
-  for (size_t it = (size_t)blockIdx.x * WAVES + (threadIdx.x >> 6); it < total; it += nw) {
-    const int j = (int)(it % g.W64), y = (int)((it / g.W64) % g.H);
-    const size_t pl = it / ((size_t)g.W64 * g.H);
-    const int x = j * 64 + lane;
-    if (x >= g.W) continue;
-    const u64 c = bits[it];
-    const size_t o = pl * g.HW + (size_t)y * g.W + x;
-    labels[o] = ((c >> lane) & 1ull) ? parent[pl * g.HW + parent[o]] + 1 : 0;      // pixel -> run start -> root (a root points at itself)
-  }
-}
-
 // ---- per-run kernels, a thread per word
 // area[root] += run length; a run that starts at its root registers the component (the root is its component's smallest index, so the pixel
 // before it is clear and the root starts a run).  cap = the list's capacity, ceil(H / 2) * ceil(W / 2), the most 8-connected components a plane holds
-__global__ __launch_bounds__(NT) void area_kernel(const u64* __restrict__ bits, int P, Geo g, const int* __restrict__ parent, int* __restrict__ area,
+__global__ __launch_bounds__(NT) void area_kernel(const u64* __restrict__ bits, int P, BitGeo g, const int* __restrict__ parent, int* __restrict__ area,
                                                   int* __restrict__ list, int* __restrict__ nroots, int cap) {
   const size_t total = (size_t)P * g.H * g.W64;
   for (size_t it = (size_t)blockIdx.x * NT + threadIdx.x; it < total; it += (size_t)gridDim.x * NT) {
@@ -234,7 +94,7 @@ __global__ __launch_bounds__(NT) void area_kernel(const u64* __restrict__ bits, 
 // keys are distinct.  Round i takes the largest key below round i - 1's.  The k-th largest area for k > 8 is a binary search on the value with a
 // count per step.  thr = max(k-th largest area or 0, min_area); table_kept: ncomp and the table describe the components with area >= thr.
 __global__ __launch_bounds__(SEL_NT) void select_kernel(const int* __restrict__ area, const int* __restrict__ list, const int* __restrict__ nroots,
-                                                        Geo g, int cap, int keep, int min_area, int table_kept, int* __restrict__ thr_out,
+                                                        BitGeo g, int cap, int keep, int min_area, int table_kept, int* __restrict__ thr_out,
                                                         int* __restrict__ ncomp, int* __restrict__ top) {
   __shared__ u64 red[SEL_NT];
   __shared__ u64 keys[TOPK];
@@ -306,7 +166,7 @@ __global__ __launch_bounds__(SEL_NT) void select_kernel(const int* __restrict__ 
   }
 }
 
-__global__ __launch_bounds__(NT) void bbox_kernel(const u64* __restrict__ bits, int P, Geo g, const int* __restrict__ parent, int* __restrict__ top) {
+__global__ __launch_bounds__(NT) void bbox_kernel(const u64* __restrict__ bits, int P, BitGeo g, const int* __restrict__ parent, int* __restrict__ top) {
   const size_t total = (size_t)P * g.H * g.W64;
   for (size_t it = (size_t)blockIdx.x * NT + threadIdx.x; it < total; it += (size_t)gridDim.x * NT) {
     u64 c = bits[it];
@@ -332,28 +192,8 @@ __global__ __launch_bounds__(NT) void bbox_kernel(const u64* __restrict__ bits, 
   }
 }
 
-__global__ __launch_bounds__(NT) void keep_kernel(const u64* __restrict__ bits, int P, Geo g, const int* __restrict__ parent, const int* __restrict__ area,
-                                                  const int* __restrict__ thr, u64* __restrict__ kept) {
-  const size_t total = (size_t)P * g.H * g.W64;
-  for (size_t it = (size_t)blockIdx.x * NT + threadIdx.x; it < total; it += (size_t)gridDim.x * NT) {
-    u64 c = bits[it], o = 0ull;
-    if (c) {
-      const int j = (int)(it % g.W64), y = (int)((it / g.W64) % g.H);
-      const size_t pl = it / ((size_t)g.W64 * g.H);
-      const int p0 = y * g.W + j * 64, th = thr[pl];
-      while (c) {
-        const int s = ctz64(c), len = runlen(c, s);
-        const u64 m = runmask(s, len);
-        if (area[pl * g.HW + parent[pl * g.HW + p0 + s]] >= th) o |= m;
-        c &= ~m;
-      }
-    }
-    kept[it] = o;
-  }
-}
-
 // hole fill, after init / merge / flatten on the complement: area[root] (0 since init) becomes 1 for background components on the frame border
-__global__ __launch_bounds__(NT) void border_kernel(const u64* __restrict__ bits, int P, Geo g, const int* __restrict__ parent, int* __restrict__ area) {
+__global__ __launch_bounds__(NT) void border_kernel(const u64* __restrict__ bits, int P, BitGeo g, const int* __restrict__ parent, int* __restrict__ area) {
   const size_t total = (size_t)P * g.H * g.W64;
   for (size_t it = (size_t)blockIdx.x * NT + threadIdx.x; it < total; it += (size_t)gridDim.x * NT) {
     const int j = (int)(it % g.W64), y = (int)((it / g.W64) % g.H);
@@ -372,7 +212,7 @@ __global__ __launch_bounds__(NT) void border_kernel(const u64* __restrict__ bits
   }
 }
 
-__global__ __launch_bounds__(NT) void fill_kernel(u64* __restrict__ bits, int P, Geo g, const int* __restrict__ parent, const int* __restrict__ area) {
+__global__ __launch_bounds__(NT) void fill_kernel(u64* __restrict__ bits, int P, BitGeo g, const int* __restrict__ parent, const int* __restrict__ area) {
   const size_t total = (size_t)P * g.H * g.W64;
   for (size_t it = (size_t)blockIdx.x * NT + threadIdx.x; it < total; it += (size_t)gridDim.x * NT) {
     const int j = (int)(it % g.W64), y = (int)((it / g.W64) % g.H);
@@ -392,8 +232,6 @@ __global__ __launch_bounds__(NT) void fill_kernel(u64* __restrict__ bits, int P,
 
 namespace {
 
-size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 struct Scratch {
   int *parent, *area, *list, *nroots, *thr;
   u64 *a, *b;
@@ -405,23 +243,17 @@ Scratch carve(void* base, size_t P, int H, int W) {
   Scratch s;
   const size_t HW = (size_t)H * W, W64 = ((size_t)W + 63) / 64;
   s.cap = (int)((((size_t)H + 1) / 2) * (((size_t)W + 1) / 2));
-  const uintptr_t p = (uintptr_t)base;      // integer arithmetic: the size query carves from a null base
-  size_t o = 0;
-  s.parent = (int*)(p + o); o += al256(P * HW * sizeof(int));
-  s.area = (int*)(p + o); o += al256(P * HW * sizeof(int));
-  s.list = (int*)(p + o); o += al256(P * (size_t)s.cap * sizeof(int));
-  s.nroots = (int*)(p + o); o += al256(P * sizeof(int));
-  s.thr = (int*)(p + o); o += al256(P * sizeof(int));
-  s.a = (u64*)(p + o); o += al256(P * H * W64 * sizeof(u64));
-  s.b = (u64*)(p + o); o += al256(P * H * W64 * sizeof(u64));
-  s.bytes = o;
+  Carver cv(base);
+  s.parent = cv.take<int>(P * HW);
+  s.area = cv.take<int>(P * HW);
+  s.list = cv.take<int>(P * (size_t)s.cap);
+  s.nroots = cv.take<int>(P);
+  s.thr = cv.take<int>(P);
+  s.a = cv.take<u64>(P * H * W64);
+  s.b = cv.take<u64>(P * H * W64);
+  s.bytes = cv.used;
   return s;
 }
-
-Geo geo(int H, int W) { return Geo{H, W, (W + 63) / 64, H * W}; }
-
-unsigned wave_grid(size_t words) { return (unsigned)std::min<size_t>((words + WAVES - 1) / WAVES, MAX_GRID); }
-unsigned word_grid(size_t words) { return (unsigned)std::min<size_t>((words + NT - 1) / NT, MAX_GRID); }
 
 Elem ellipse(int k) {   // OpenCV 4.8.1 getStructuringElement(MORPH_ELLIPSE): postprocess.ellipse states the same
   Elem e;
@@ -440,16 +272,10 @@ Elem ellipse(int k) {   // OpenCV 4.8.1 getStructuringElement(MORPH_ELLIPSE): po
 }
 
 // init / merge / flatten of the planes in `bits` (inv: of their complement inside the frame)
-void label_planes(const u64* bits, int P, const Geo& g, int inv, int conn8, const Scratch& s, hipStream_t st) {
-  const unsigned gw = wave_grid((size_t)P * g.H * g.W64);
-  hipLaunchKernelGGL(init_kernel, dim3(gw), dim3(NT), 0, st, bits, P, g, inv, s.parent, s.area);
-  hipLaunchKernelGGL(merge_kernel, dim3(gw), dim3(NT), 0, st, bits, P, g, inv, conn8, s.parent);
-  hipLaunchKernelGGL(flatten_kernel, dim3(gw), dim3(NT), 0, st, bits, P, g, inv, s.parent);
-}
-
-void pack(const float* stack, int N, const Geo& g, int C, u64* bits, hipStream_t st) {
-  const int vec = (C == 4 && ((uintptr_t)stack & 15) == 0) ? 1 : 0;
-  hipLaunchKernelGGL(pack_kernel, dim3(wave_grid((size_t)N * g.H * g.W64)), dim3(NT), 0, st, stack, N, g, C, bits, vec);
+void label_planes(const u64* bits, int P, const BitGeo& g, int inv, int conn8, const Scratch& s, hipStream_t st) {
+  launch_ccl_init(bits, P, g, inv, s.parent, s.area, nullptr, st);
+  launch_ccl_merge(bits, P, g, inv, conn8, s.parent, st);
+  launch_ccl_flatten(bits, P, g, inv, s.parent, st);
 }
 
 }  // namespace
@@ -458,18 +284,18 @@ size_t components_scratch_bytes(size_t planes, int H, int W) { return carve(null
 
 hipError_t launch_stack_components(const float* stack, int N, int H, int W, int C, void* scratch, int* labels, int* ncomp, int* top, hipStream_t st) {
   const int P = N * C;
-  const Geo g = geo(H, W);
+  const BitGeo g = bit_geo(1, H, W);
   const Scratch s = carve(scratch, P, H, W);
   const size_t words = (size_t)P * g.H * g.W64;
-  pack(stack, N, g, C, s.a, st);
+  launch_bits_pack(stack, N, g, C, C, 1, s.a, st);
   label_planes(s.a, P, g, 0, 1, s, st);
-  if (labels) hipLaunchKernelGGL(labels_kernel, dim3(wave_grid(words)), dim3(NT), 0, st, s.a, P, g, s.parent, labels);
+  if (labels) launch_ccl_labels(s.a, P, g, s.parent, labels, st);
   if (ncomp || top) {
     hipError_t e = hipMemsetAsync(s.nroots, 0, (size_t)P * sizeof(int), st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(area_kernel, dim3(word_grid(words)), dim3(NT), 0, st, s.a, P, g, s.parent, s.area, s.list, s.nroots, s.cap);
+    hipLaunchKernelGGL(area_kernel, dim3(item_grid(words)), dim3(NT), 0, st, s.a, P, g, s.parent, s.area, s.list, s.nroots, s.cap);
     hipLaunchKernelGGL(select_kernel, dim3(P), dim3(SEL_NT), 0, st, s.area, s.list, s.nroots, g, s.cap, 0, 0, 0, (int*)nullptr, ncomp, top);
-    if (top) hipLaunchKernelGGL(bbox_kernel, dim3(word_grid(words)), dim3(NT), 0, st, s.a, P, g, s.parent, top);
+    if (top) hipLaunchKernelGGL(bbox_kernel, dim3(item_grid(words)), dim3(NT), 0, st, s.a, P, g, s.parent, top);
   }
   return hipGetLastError();
 }
@@ -477,16 +303,16 @@ hipError_t launch_stack_components(const float* stack, int N, int H, int W, int 
 hipError_t launch_stack_cleanup(const float* stack, int N, int H, int W, int C, int smooth_k, int keep, int min_area, int fill_holes, void* scratch,
                                 float* out, int* ncomp, int* top, hipStream_t st) {
   const int P = N * C;
-  const Geo g = geo(H, W);
+  const BitGeo g = bit_geo(1, H, W);
   const Scratch s = carve(scratch, P, H, W);
   const size_t words = (size_t)P * g.H * g.W64;
   u64 *cur = s.a, *other = s.b;
-  pack(stack, N, g, C, cur, st);
+  launch_bits_pack(stack, N, g, C, C, 1, cur, st);
   if (smooth_k > 1) {                                        // erode, dilate (open); dilate, erode (close); dilate
     const Elem el = ellipse(smooth_k);
     const int ero[5] = {1, 0, 0, 1, 0};
     for (int i = 0; i < 5; ++i) {
-      hipLaunchKernelGGL(morph_kernel, dim3(word_grid(words)), dim3(NT), 0, st, cur, other, P, g, el, ero[i]);
+      hipLaunchKernelGGL(morph_kernel, dim3(item_grid(words)), dim3(NT), 0, st, cur, other, P, g, el, ero[i]);
       std::swap(cur, other);
     }
   }
@@ -495,21 +321,20 @@ hipError_t launch_stack_cleanup(const float* stack, int N, int H, int W, int C, 
     label_planes(cur, P, g, 0, 1, s, st);
     hipError_t e = hipMemsetAsync(s.nroots, 0, (size_t)P * sizeof(int), st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(area_kernel, dim3(word_grid(words)), dim3(NT), 0, st, cur, P, g, s.parent, s.area, s.list, s.nroots, s.cap);
+    hipLaunchKernelGGL(area_kernel, dim3(item_grid(words)), dim3(NT), 0, st, cur, P, g, s.parent, s.area, s.list, s.nroots, s.cap);
     hipLaunchKernelGGL(select_kernel, dim3(P), dim3(SEL_NT), 0, st, s.area, s.list, s.nroots, g, s.cap, keep, min_area, 1, s.thr, ncomp, top);
-    if (top) hipLaunchKernelGGL(bbox_kernel, dim3(word_grid(words)), dim3(NT), 0, st, cur, P, g, s.parent, top);
+    if (top) hipLaunchKernelGGL(bbox_kernel, dim3(item_grid(words)), dim3(NT), 0, st, cur, P, g, s.parent, top);
     if (filter) {
-      hipLaunchKernelGGL(keep_kernel, dim3(word_grid(words)), dim3(NT), 0, st, cur, P, g, s.parent, s.area, s.thr, other);
+      launch_ccl_keep(cur, P, g, s.parent, s.area, nullptr, s.thr, 1, other, st);
       std::swap(cur, other);
     }
   }
   if (fill_holes) {                                          // the same labelling on the complement, 4-connected
     label_planes(cur, P, g, 1, 0, s, st);
-    hipLaunchKernelGGL(border_kernel, dim3(word_grid(words)), dim3(NT), 0, st, cur, P, g, s.parent, s.area);
-    hipLaunchKernelGGL(fill_kernel, dim3(word_grid(words)), dim3(NT), 0, st, cur, P, g, s.parent, s.area);
+    hipLaunchKernelGGL(border_kernel, dim3(item_grid(words)), dim3(NT), 0, st, cur, P, g, s.parent, s.area);
+    hipLaunchKernelGGL(fill_kernel, dim3(item_grid(words)), dim3(NT), 0, st, cur, P, g, s.parent, s.area);
   }
-  const int vec = (C == 4 && ((uintptr_t)out & 15) == 0) ? 1 : 0;
-  hipLaunchKernelGGL(unpack_kernel, dim3(wave_grid((size_t)N * g.H * g.W64)), dim3(NT), 0, st, cur, N, g, C, out, vec);
+  launch_bits_unpack(cur, N, g, C, C, 1, out, st);
   return hipGetLastError();
 }
 

@@ -3,12 +3,11 @@
 // family (HD, HD95, ASSD), the smallest distance between two classes with the pixel that attains it, and the overlap counts of the same
 // planes.  No reference counterpart: the reference reports overlap scores only (DESIGN.md section 5i states the definitions).
 //
-// A plane is one (slice, channel) pair of the float32 stack [N][H][W][C], any value != 0 set.  Planes live as the BIT PLANES of components.hip:
-// row y is W64 = ceil(W / 64) 64-bit words, bit i of word j = pixel 64 j + i, bits past the frame always 0.  Everything is integer arithmetic on
+// A plane is one (slice, channel) pair of the float32 stack [N][H][W][C], any value != 0 set.  Planes live as the bit planes of bitplanes.h, every
+// plane on its own (its geometry with D = 1); pack and unpack are the shared kernels of bitplanes.hip.  Everything is integer arithmetic on
 // SQUARED distances: d2 = dx^2 + dy^2 < 2^25 for H, W <= 4096, exact in int32; no floating point takes part in any decision.  Every phase that
 // needs a grid-wide order is a launch of its own on the caller's stream; no workgroup waits on another, no spin, no cooperative launch.
 //
-//   pack      stack -> bits (the ballot pack of components.hip, kept here as a copy of its own)
 //   part      the plane a call works on, a thread per word: `set` = the plane, `clear` = its complement inside the frame, `boundary` =
 //             m & ~erode(m) with the 4-neighbour cross, outside the frame clear (so a set pixel on the frame edge is boundary): the word ANDed with
 //             the words above and below and with itself shifted by one bit either way, the neighbours' edge bits shifted in.  A word that is not
@@ -29,34 +28,19 @@
 // neighbours outside the frame read as clear.  A wrong argument gives a wrong number, never a stray access.
 #include <algorithm>
 
-#include "common.h"
+#include "bitplanes.h"
 #include "kernels.h"
 
 namespace octseg {
 
 namespace {
 
-constexpr int NT = 256, WAVES = NT / 64;
-constexpr unsigned MAX_GRID = 1u << 20;
 constexpr int DIST_NONE = 0x7fffffff;
 constexpr int G_NONE = 0xFFFF;
 constexpr int MAX_W = 4096;
 constexpr int COL_ROWS = 8;
 
-typedef unsigned long long u64;
 typedef unsigned short u16;
-
-struct Geo { int H, W, W64, HW; };
-
-__device__ __forceinline__ u64 inmask(int j, int W) {
-  const int n = W - j * 64;
-  return n >= 64 ? ~0ull : ((1ull << n) - 1ull);
-}
-// word j of row y, 0 outside the frame
-__device__ __forceinline__ u64 rdw(const u64* __restrict__ plane, int y, int j, const Geo& g) {
-  if (y < 0 || y >= g.H || j < 0 || j >= g.W64) return 0ull;
-  return plane[(size_t)y * g.W64 + j];
-}
 
 // min over x' of (x - x')^2 + row[x']^2 for one query pixel; row: the W values of g in LDS.  k^2 and g^2 are below 2^24: the sum fits int32.
 __device__ __forceinline__ int row_min(const u16* row, int W, int x) {
@@ -75,54 +59,9 @@ __device__ __forceinline__ int row_min(const u16* row, int W, int x) {
 
 }  // namespace
 
-// ---- stack <-> bit planes (components.hip's pack / unpack)
-__global__ __launch_bounds__(NT) void dist_pack_kernel(const float* __restrict__ stack, int N, Geo g, int C, u64* __restrict__ bits, int vec) {
-  const int lane = threadIdx.x & 63;
-  const size_t nw = (size_t)gridDim.x * WAVES, total = (size_t)N * g.H * g.W64;
-  for (size_t it = (size_t)blockIdx.x * WAVES + (threadIdx.x >> 6); it < total; it += nw) {     // wave-uniform
-    const int j = (int)(it % g.W64), y = (int)((it / g.W64) % g.H);
-    const size_t n = it / ((size_t)g.W64 * g.H);
-    const int x = j * 64 + lane;
-    const bool ok = x < g.W;
-    const float* px = stack + ((n * g.H + y) * (size_t)g.W + (ok ? x : g.W - 1)) * C;
-    if (vec) {
-      const float4 v = *(const float4*)px;
-      const u64 w0 = __ballot(ok && v.x != 0.f), w1 = __ballot(ok && v.y != 0.f), w2 = __ballot(ok && v.z != 0.f), w3 = __ballot(ok && v.w != 0.f);
-      if (lane < 4) bits[((n * 4 + lane) * g.H + y) * (size_t)g.W64 + j] = lane == 0 ? w0 : lane == 1 ? w1 : lane == 2 ? w2 : w3;
-    } else {
-      for (int c = 0; c < C; ++c) {
-        const u64 w = __ballot(ok && px[c] != 0.f);
-        if (lane == 0) bits[((n * C + c) * g.H + y) * (size_t)g.W64 + j] = w;
-      }
-    }
-  }
-}
-
-__global__ __launch_bounds__(NT) void dist_unpack_kernel(const u64* __restrict__ bits, int N, Geo g, int C, float* __restrict__ out, int vec) {
-  const int lane = threadIdx.x & 63;
-  const size_t nw = (size_t)gridDim.x * WAVES, total = (size_t)N * g.H * g.W64;
-  for (size_t it = (size_t)blockIdx.x * WAVES + (threadIdx.x >> 6); it < total; it += nw) {
-    const int j = (int)(it % g.W64), y = (int)((it / g.W64) % g.H);
-    const size_t n = it / ((size_t)g.W64 * g.H);
-    const int x = j * 64 + lane;
-    if (x >= g.W) continue;
-    float* px = out + ((n * g.H + y) * (size_t)g.W + x) * C;
-    if (vec) {
-      float4 v;
-      v.x = (float)((bits[((n * 4 + 0) * g.H + y) * (size_t)g.W64 + j] >> lane) & 1ull);
-      v.y = (float)((bits[((n * 4 + 1) * g.H + y) * (size_t)g.W64 + j] >> lane) & 1ull);
-      v.z = (float)((bits[((n * 4 + 2) * g.H + y) * (size_t)g.W64 + j] >> lane) & 1ull);
-      v.w = (float)((bits[((n * 4 + 3) * g.H + y) * (size_t)g.W64 + j] >> lane) & 1ull);
-      *(float4*)px = v;
-    } else {
-      for (int c = 0; c < C; ++c) px[c] = (float)((bits[((n * C + c) * g.H + y) * (size_t)g.W64 + j] >> lane) & 1ull);
-    }
-  }
-}
-
 // ---- the part of every plane a call works on, a thread per word.  part: 0 set, 1 clear, 2 boundary.  any (may be null): any[plane] = 1 when the
 // result holds a pixel; cleared by the caller beforehand
-__global__ __launch_bounds__(NT) void dist_part_kernel(const u64* __restrict__ src, u64* __restrict__ dst, int P, Geo g, int part, int* __restrict__ any) {
+__global__ __launch_bounds__(NT) void dist_part_kernel(const u64* __restrict__ src, u64* __restrict__ dst, int P, BitGeo g, int part, int* __restrict__ any) {
   const size_t total = (size_t)P * g.H * g.W64;
   for (size_t it = (size_t)blockIdx.x * NT + threadIdx.x; it < total; it += (size_t)gridDim.x * NT) {
     const int j = (int)(it % g.W64), y = (int)((it / g.W64) % g.H);
@@ -148,7 +87,7 @@ __global__ __launch_bounds__(NT) void dist_part_kernel(const u64* __restrict__ s
 }
 
 // ---- column pass, a thread per (plane, column)
-__global__ __launch_bounds__(NT) void dist_column_kernel(const u64* __restrict__ bits, int P, Geo g, const int* __restrict__ any, u16* __restrict__ gcol) {
+__global__ __launch_bounds__(NT) void dist_column_kernel(const u64* __restrict__ bits, int P, BitGeo g, const int* __restrict__ any, u16* __restrict__ gcol) {
   const size_t total = (size_t)P * g.W;
   for (size_t it = (size_t)blockIdx.x * NT + threadIdx.x; it < total; it += (size_t)gridDim.x * NT) {
     const int x = (int)(it % g.W);
@@ -187,7 +126,7 @@ __global__ __launch_bounds__(NT) void dist_column_kernel(const u64* __restrict__
 }
 
 // ---- full map: a workgroup per (plane, row), the row of g in LDS
-__global__ __launch_bounds__(NT) void dist_map_kernel(const u16* __restrict__ gcol, const int* __restrict__ any, int P, Geo g, int* __restrict__ d2) {
+__global__ __launch_bounds__(NT) void dist_map_kernel(const u16* __restrict__ gcol, const int* __restrict__ any, int P, BitGeo g, int* __restrict__ d2) {
   __shared__ u16 row[MAX_W];
   const size_t total = (size_t)P * g.H;
   for (size_t it = blockIdx.x; it < total; it += gridDim.x) {      // workgroup-uniform
@@ -207,7 +146,7 @@ __global__ __launch_bounds__(NT) void dist_map_kernel(const u16* __restrict__ gc
 
 // ---- counts: a workgroup per (slice, pair).  counts [N][P][2] = query, target pixels; overlap [N][P][3] = |a & b|, |a|, |b| of the raw planes
 __global__ __launch_bounds__(NT) void dist_count_kernel(const u64* __restrict__ rawa, const u64* __restrict__ rawb, const u64* __restrict__ qbits,
-                                                        const u64* __restrict__ tbits, int N, Geo g, int Ca, int Cb, const int* __restrict__ pairs,
+                                                        const u64* __restrict__ tbits, int N, BitGeo g, int Ca, int Cb, const int* __restrict__ pairs,
                                                         int P, int* __restrict__ counts, int* __restrict__ overlap) {
   __shared__ int red[5][NT];
   const size_t total = (size_t)N * P, words = (size_t)g.H * g.W64;
@@ -242,7 +181,7 @@ __global__ __launch_bounds__(NT) void dist_count_kernel(const u64* __restrict__ 
 
 // ---- d2 at the query pixels: a workgroup per (slice, pair, row).  keys (with offsets, cursor, capacity, overflow) and / or minout
 __global__ __launch_bounds__(NT) void dist_query_kernel(const u64* __restrict__ qbits, const u16* __restrict__ gcol, const int* __restrict__ any, int N,
-                                                        Geo g, int Ca, int Cb, const int* __restrict__ pairs, int P, long long seg0,
+                                                        BitGeo g, int Ca, int Cb, const int* __restrict__ pairs, int P, long long seg0,
                                                         const long long* __restrict__ offsets, int* __restrict__ cursor, long long* __restrict__ keys,
                                                         long long capacity, int* __restrict__ overflow, u64* __restrict__ minout) {
   __shared__ u16 row[MAX_W];
@@ -293,8 +232,6 @@ __global__ __launch_bounds__(NT) void dist_query_kernel(const u64* __restrict__ 
 
 namespace {
 
-size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 struct Scratch {
   u64 *rawa, *rawb, *qa, *tb;
   u16* g;
@@ -307,36 +244,26 @@ Scratch carve(void* base, size_t N, int H, int W, int Ca, int Cb, int pairs) {
   Scratch s;
   const size_t HW = (size_t)H * W, words = (size_t)H * (((size_t)W + 63) / 64);
   const size_t Pa = N * Ca, Pb = N * Cb, Pt = Cb ? Pb : Pa;
-  const uintptr_t p = (uintptr_t)base;
-  size_t o = 0;
-  s.rawa = (u64*)(p + o); o += al256(Pa * words * sizeof(u64));
-  s.qa = (u64*)(p + o); o += al256(Pa * words * sizeof(u64));
-  s.rawb = (u64*)(p + o); o += al256(Pb * words * sizeof(u64));
-  s.tb = (u64*)(p + o); o += al256(Pb * words * sizeof(u64));
-  s.g = (u16*)(p + o); o += al256(Pt * HW * sizeof(u16));
-  s.any = (int*)(p + o); o += al256(Pt * sizeof(int));
-  s.cursor = (int*)(p + o); o += al256(N * (size_t)pairs * sizeof(int));
-  s.bytes = o;
+  Carver cv(base);
+  s.rawa = cv.take<u64>(Pa * words);
+  s.qa = cv.take<u64>(Pa * words);
+  s.rawb = cv.take<u64>(Pb * words);
+  s.tb = cv.take<u64>(Pb * words);
+  s.g = cv.take<u16>(Pt * HW);
+  s.any = cv.take<int>(Pt);
+  s.cursor = cv.take<int>(N * (size_t)pairs);
+  s.bytes = cv.used;
   return s;
 }
 
-Geo geo(int H, int W) { return Geo{H, W, (W + 63) / 64, H * W}; }
-
-unsigned wave_grid(size_t words) { return (unsigned)std::min<size_t>((words + WAVES - 1) / WAVES, MAX_GRID); }
-unsigned item_grid(size_t items) { return (unsigned)std::min<size_t>((items + NT - 1) / NT, MAX_GRID); }
 unsigned block_grid(size_t blocks) { return (unsigned)std::min<size_t>(blocks, MAX_GRID); }
 
-void pack(const float* stack, int N, const Geo& g, int C, u64* bits, hipStream_t st) {
-  const int vec = (C == 4 && ((uintptr_t)stack & 15) == 0) ? 1 : 0;
-  hipLaunchKernelGGL(dist_pack_kernel, dim3(wave_grid((size_t)N * g.H * g.W64)), dim3(NT), 0, st, stack, N, g, C, bits, vec);
-}
-
 // pack both stacks, derive the query planes of src and the target planes of dst (any = which target planes hold a pixel)
-hipError_t prepare_pair(const float* src, const float* dst, int N, const Geo& g, int Ca, int Cb, int src_part, int dst_part, const Scratch& s,
+hipError_t prepare_pair(const float* src, const float* dst, int N, const BitGeo& g, int Ca, int Cb, int src_part, int dst_part, const Scratch& s,
                         hipStream_t st) {
   const size_t wa = (size_t)N * Ca * g.H * g.W64, wb = (size_t)N * Cb * g.H * g.W64;
-  pack(src, N, g, Ca, s.rawa, st);
-  pack(dst, N, g, Cb, s.rawb, st);
+  launch_bits_pack(src, N, g, Ca, Ca, 1, s.rawa, st);
+  launch_bits_pack(dst, N, g, Cb, Cb, 1, s.rawb, st);
   hipError_t e = hipMemsetAsync(s.any, 0, (size_t)N * Cb * sizeof(int), st);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(dist_part_kernel, dim3(item_grid(wa)), dim3(NT), 0, st, s.rawa, s.qa, N * Ca, g, src_part, (int*)nullptr);
@@ -349,20 +276,19 @@ hipError_t prepare_pair(const float* src, const float* dst, int N, const Geo& g,
 size_t distance_scratch_bytes(size_t N, int H, int W, int Ca, int Cb, int pairs) { return carve(nullptr, N, H, W, Ca, Cb, pairs).bytes; }
 
 hipError_t launch_stack_boundary(const float* stack, int N, int H, int W, int C, void* scratch, float* out, hipStream_t st) {
-  const Geo g = geo(H, W);
+  const BitGeo g = bit_geo(1, H, W);
   const Scratch s = carve(scratch, N, H, W, C, 0, 0);
-  pack(stack, N, g, C, s.rawa, st);
+  launch_bits_pack(stack, N, g, C, C, 1, s.rawa, st);
   hipLaunchKernelGGL(dist_part_kernel, dim3(item_grid((size_t)N * C * g.H * g.W64)), dim3(NT), 0, st, s.rawa, s.qa, N * C, g, 2, (int*)nullptr);
-  const int vec = (C == 4 && ((uintptr_t)out & 15) == 0) ? 1 : 0;
-  hipLaunchKernelGGL(dist_unpack_kernel, dim3(wave_grid((size_t)N * g.H * g.W64)), dim3(NT), 0, st, s.qa, N, g, C, out, vec);
+  launch_bits_unpack(s.qa, N, g, C, C, 1, out, st);
   return hipGetLastError();
 }
 
 hipError_t launch_stack_distance(const float* stack, int N, int H, int W, int C, int to, void* scratch, int* d2, hipStream_t st) {
-  const Geo g = geo(H, W);
+  const BitGeo g = bit_geo(1, H, W);
   const int P = N * C;
   const Scratch s = carve(scratch, N, H, W, C, 0, 0);
-  pack(stack, N, g, C, s.rawa, st);
+  launch_bits_pack(stack, N, g, C, C, 1, s.rawa, st);
   hipError_t e = hipMemsetAsync(s.any, 0, (size_t)P * sizeof(int), st);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(dist_part_kernel, dim3(item_grid((size_t)P * g.H * g.W64)), dim3(NT), 0, st, s.rawa, s.qa, P, g, to, s.any);
@@ -373,7 +299,7 @@ hipError_t launch_stack_distance(const float* stack, int N, int H, int W, int C,
 
 hipError_t launch_pair_distance_counts(const float* src, const float* dst, int N, int H, int W, int Ca, int Cb, const int* pairs, int P, int src_part,
                                        int dst_part, void* scratch, int* counts, int* overlap, hipStream_t st) {
-  const Geo g = geo(H, W);
+  const BitGeo g = bit_geo(1, H, W);
   const Scratch s = carve(scratch, N, H, W, Ca, Cb, P);
   hipError_t e = prepare_pair(src, dst, N, g, Ca, Cb, src_part, dst_part, s, st);
   if (e != hipSuccess) return e;
@@ -386,7 +312,7 @@ hipError_t launch_pair_distance_counts(const float* src, const float* dst, int N
 hipError_t launch_pair_distance_query(const float* src, const float* dst, int N, int H, int W, int Ca, int Cb, const int* pairs, int P, int src_part,
                                       int dst_part, void* scratch, long long seg0, const long long* offsets, long long* keys, long long capacity,
                                       int* overflow, unsigned long long* minout, hipStream_t st) {
-  const Geo g = geo(H, W);
+  const BitGeo g = bit_geo(1, H, W);
   const Scratch s = carve(scratch, N, H, W, Ca, Cb, P);
   hipError_t e = prepare_pair(src, dst, N, g, Ca, Cb, src_part, dst_part, s, st);
   if (e != hipSuccess) return e;

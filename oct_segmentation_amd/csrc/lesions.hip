@@ -4,71 +4,43 @@
 // connects (`overlap`: the frame pitch of a pullback is an order of magnitude above the pixel pitch) or the whole 3 x 3 above / below (`full`,
 // 26-connected).  The label of a lesion is 1 + n * H * W + y * W + x of its first voxel in raster order.
 //
-// The bits live as in components.hip, one volume after the other: word j of row y of slice n of channel c at ((c * N + n) * H + y) * W64 + j, bit i =
-// pixel 64 j + i, bits past the frame 0; an all-zero word is the early exit of every kernel.  parent / vox / zmax are int32 [C][N * H * W] and hold
-// VOLUME indices v = n * H * W + y * W + x.  Every phase that needs a grid-wide order is a launch of its own on the caller's stream; no workgroup
-// ever waits on another, there is no flag, no spin, no cooperative launch and no inline assembly; nothing is allocated.
+// The bits are the bit planes of bitplanes.h, one volume after the other: its geometry "S sets of D planes" with S = C, D = N, so word j of row y of
+// slice n of channel c stands at ((c * N + n) * H + y) * W64 + j, and parent / vox / zmax are int32 [C][N * H * W] and hold VOLUME indices
+// v = n * H * W + y * W + x.  Every phase that needs a grid-wide order is a launch of its own on the caller's stream; no workgroup ever waits on
+// another, there is no flag, no spin, no cooperative launch and no inline assembly; nothing is allocated.
 //
-//   pack        stack -> bits of every channel in one pass over the interleaved stack (a wave takes 64 pixels of a row, a ballot per channel)
-//   init        parent[v] = first voxel of v's horizontal run inside its word; of a run start, vox = 0 and zmax = its own slice
-//   merge       inside every slice: components.hip's 8-connected merge with volume indices (a slice's first row has no row above)
-//   across      a thread per word of slice n >= 1.  overlap: m = c & (the same word of slice n - 1), one unite per maximal run of m with the voxel
-//               straight above: both sides of a run are horizontal runs, connected inside their slices already.  full: the same for each of the
-//               nine words (rows y - 1 .. y + 1 of slice n - 1, each as it is and shifted by +-1 with the neighbour words' bits shifted in), the
-//               partner of a run's first bit being that one source voxel.  (One unite per run of the OR of the nine would NOT do: two adjacent
-//               bits may see different source voxels, (y - 1, x - 1) and (y + 1, x + 2), that nothing connects in slice n - 1.)
-//   flatten     parent[run start] = root; the other voxels of a run keep pointing at their run start.  root = the smallest index = first voxel.
+// pack / unpack, init (of a run start, vox = 0 and zmax = its own slice), the 8-connected merge inside every slice, flatten, labels and keep (voxels
+// >= threshold and z1 - z0 + 1 >= min_slices) are the shared kernels of bitplanes.hip, where the termination argument of the union-find loops
+// stands; the unites of `across` fall under it because slice n - 1's voxels are smaller indices of the same array.  Here:
+//
+//   across      between init / merge and flatten: a thread per word of slice n >= 1.  overlap: m = c & (the same word of slice n - 1), one unite per
+//               maximal run of m with the voxel straight above: both sides of a run are horizontal runs, connected inside their slices already.
+//               full: the same for each of the nine words (rows y - 1 .. y + 1 of slice n - 1, each as it is and shifted by +-1 with the neighbour
+//               words' bits shifted in), the partner of a run's first bit being that one source voxel.  (One unite per run of the OR of the nine
+//               would NOT do: two adjacent bits may see different source voxels, (y - 1, x - 1) and (y + 1, x + 2), that nothing connects in
+//               slice n - 1.)
 //   count       a thread per word: vox[root] += run length, zmax[root] = max(slice), summed per root inside the wave before one lane's atomic; a
 //               run that starts at its root appends the root to the channel's lesion list (capacity N * ceil(H / 2) * ceil(W / 2), the most
 //               components a volume holds under either rule)
 //   select      ONE workgroup per channel: the threshold t (the keep-th largest voxel count, by bisection on the value), nles, the 32 largest kept
 //               lesions by (voxels descending, first voxel ascending) with z0 = first voxel / (H * W) and z1 = zmax
 //   extents     runs of ranked lesions reduce the bounding box (atomicMin / atomicMax) and add to profile[rank][slice]
-//   keep        kept bits = runs whose lesion has voxels >= threshold and z1 - z0 + 1 >= min_slices
-//   unpack      bits -> float32 0.0 / 1.0 in the stack's layout;   labels: parent -> int32 [C][N][H][W], background 0
 //
-// TERMINATION of every union-find loop, as in components.hip (find_root / unite are the same functions, unionfind.h): parent[x] <= x always (init
-// writes a run start, atomicMin only lowers a value), a non-root has parent[x] < x, so a find walks strictly downwards and ends after at most
-// N * H * W steps; a unite either links a root (done) or continues with a strictly smaller pair.  The cross-slice unites keep all of this because
-// the indices are global to the volume: slice n - 1's voxels are simply smaller indices of the same array.  A stale read of parent yields an
-// older, larger ancestor of the same set: the walk still descends, and the atomicMin that links returns the true value, so a lost race is seen and
-// repeated, never missed.  The other loops: run loops clear at least one set bit of a 64-bit word per round; grid-stride loops advance by the
-// grid; the bisection of select halves hi - lo every round (at most 31 rounds); the ranking runs 32 rounds; the in-wave reduction of count and
-// extents handles one destination per round and clears at least its leader's bit of a 64-bit ballot.
+// The other loops: run loops clear at least one set bit of a 64-bit word per round; grid-stride loops advance by the grid; the bisection of select
+// halves hi - lo every round (at most 31 rounds); the ranking runs 32 rounds; the in-wave reduction of count and extents handles one destination
+// per round and clears at least its leader's bit of a 64-bit ballot.
 #include <algorithm>
 
-#include "common.h"
+#include "bitplanes.h"
 #include "kernels.h"
-#include "unionfind.h"
 
 namespace octseg {
 
 namespace {
 
-constexpr int NT = 256, WAVES = NT / 64;
 constexpr int SEL_NT = 256;               // workgroup of vol_select_kernel (a power of two)
 constexpr int TOPL = 32, LCOL = 8;        // the table: voxels, first_voxel, z0, z1, y0, y1, x0, x1
-constexpr unsigned MAX_GRID = 1u << 20;
 
-struct VGeo { int N, H, W, W64, HW, NHW; size_t words; };   // words = N * H * W64, the words of one volume
-
-// word it of the C volumes -> its place
-struct Place { int c, n, y, j; };
-__device__ __forceinline__ Place place(size_t it, const VGeo& g) {
-  Place p;
-  p.j = (int)(it % g.W64);
-  const size_t row = it / g.W64;
-  p.y = (int)(row % g.H);
-  const size_t sl = row / g.H;
-  p.n = (int)(sl % g.N);
-  p.c = (int)(sl / g.N);
-  return p;
-}
-// word j of row y of a slice: 0 outside the frame
-__device__ __forceinline__ u64 rds(const u64* __restrict__ slice, int y, int j, const VGeo& g) {
-  if (y < 0 || y >= g.H || j < 0 || j >= g.W64) return 0ull;
-  return slice[(size_t)y * g.W64 + j];
-}
 // one unite per maximal run of m: voxel a0 + s with voxel a0 + s + off, s the run's first bit
 __device__ __forceinline__ void unite_runs(int* par, u64 m, int a0, int off) {
   while (m) {                                                  // every round clears the run it handled
@@ -80,143 +52,29 @@ __device__ __forceinline__ void unite_runs(int* par, u64 m, int a0, int off) {
 
 }  // namespace
 
-// ---- stack <-> bits
-__global__ __launch_bounds__(NT) void vol_pack_kernel(const float* __restrict__ stack, VGeo g, int C, u64* __restrict__ bits, int vec) {
-  const int lane = threadIdx.x & 63;
-  const size_t nw = (size_t)gridDim.x * WAVES;
-  for (size_t it = (size_t)blockIdx.x * WAVES + (threadIdx.x >> 6); it < g.words; it += nw) {     // wave-uniform
-    const Place p = place(it, g);                              // p.c == 0: `it` runs over one volume's words
-    const int x = p.j * 64 + lane;
-    const bool ok = x < g.W;
-    const float* px = stack + (((size_t)p.n * g.H + p.y) * (size_t)g.W + (ok ? x : g.W - 1)) * C;
-    if (vec) {
-      const float4 v = *(const float4*)px;
-      const u64 w0 = __ballot(ok && v.x != 0.f), w1 = __ballot(ok && v.y != 0.f), w2 = __ballot(ok && v.z != 0.f), w3 = __ballot(ok && v.w != 0.f);
-      if (lane < 4) bits[(size_t)lane * g.words + it] = lane == 0 ? w0 : lane == 1 ? w1 : lane == 2 ? w2 : w3;
-    } else {
-      for (int c = 0; c < C; ++c) {
-        const u64 w = __ballot(ok && px[c] != 0.f);
-        if (lane == 0) bits[(size_t)c * g.words + it] = w;
-      }
-    }
-  }
-}
-
-__global__ __launch_bounds__(NT) void vol_unpack_kernel(const u64* __restrict__ bits, VGeo g, int C, float* __restrict__ out, int vec) {
-  const int lane = threadIdx.x & 63;
-  const size_t nw = (size_t)gridDim.x * WAVES;
-  for (size_t it = (size_t)blockIdx.x * WAVES + (threadIdx.x >> 6); it < g.words; it += nw) {
-    const Place p = place(it, g);
-    const int x = p.j * 64 + lane;
-    if (x >= g.W) continue;
-    float* px = out + (((size_t)p.n * g.H + p.y) * (size_t)g.W + x) * C;
-    if (vec) {
-      float4 v;
-      v.x = (float)((bits[it] >> lane) & 1ull);
-      v.y = (float)((bits[g.words + it] >> lane) & 1ull);
-      v.z = (float)((bits[2 * g.words + it] >> lane) & 1ull);
-      v.w = (float)((bits[3 * g.words + it] >> lane) & 1ull);
-      *(float4*)px = v;
-    } else {
-      for (int c = 0; c < C; ++c) px[c] = (float)((bits[(size_t)c * g.words + it] >> lane) & 1ull);
-    }
-  }
-}
-
-// ---- labelling, a lane per voxel (a wave per word)
-__global__ __launch_bounds__(NT) void vol_init_kernel(const u64* __restrict__ bits, int C, VGeo g, int* __restrict__ parent, int* __restrict__ vox,
-                                                      int* __restrict__ zmax) {
-  const int lane = threadIdx.x & 63;
-  const size_t nw = (size_t)gridDim.x * WAVES, total = (size_t)C * g.words;
-  for (size_t it = (size_t)blockIdx.x * WAVES + (threadIdx.x >> 6); it < total; it += nw) {
-    const u64 c = bits[it];
-    if (!c || !((c >> lane) & 1ull)) continue;                // bits past the frame are clear: x < W below
-    const Place p = place(it, g);
-    const u64 below = ~c & ((1ull << lane) - 1ull);           // clear bits under this lane
-    const int start = below ? 64 - __clzll((long long)below) : 0;
-    const size_t o = (size_t)p.c * g.NHW + (size_t)(p.n * g.HW + p.y * g.W + p.j * 64 + lane);
-    parent[o] = p.n * g.HW + p.y * g.W + p.j * 64 + start;
-    if (lane == start) { vox[o] = 0; zmax[o] = p.n; }         // a root starts a run: only run starts are ever counted into; z1 >= z0
-  }
-}
-
-__global__ __launch_bounds__(NT) void vol_merge_kernel(const u64* __restrict__ bits, int C, VGeo g, int* __restrict__ parent) {
-  const int lane = threadIdx.x & 63;
-  const size_t nw = (size_t)gridDim.x * WAVES, total = (size_t)C * g.words;
-  for (size_t it = (size_t)blockIdx.x * WAVES + (threadIdx.x >> 6); it < total; it += nw) {
-    const u64 c = bits[it];
-    if (!c || !((c >> lane) & 1ull)) continue;
-    const Place p = place(it, g);
-    const int y = p.y, j = p.j;
-    const u64* slice = bits + ((size_t)p.c * g.N + p.n) * g.H * g.W64;
-    const u64 cl = rds(slice, y, j - 1, g), cr = rds(slice, y, j + 1, g);
-    const u64 u = rds(slice, y - 1, j, g), ul = rds(slice, y - 1, j - 1, g), ur = rds(slice, y - 1, j + 1, g);
-    const bool w = lane ? (c >> (lane - 1)) & 1ull : cl >> 63, e = lane < 63 ? (c >> (lane + 1)) & 1ull : cr & 1ull;
-    const bool n = (u >> lane) & 1ull, nwb = lane ? (u >> (lane - 1)) & 1ull : ul >> 63, neb = lane < 63 ? (u >> (lane + 1)) & 1ull : ur & 1ull;
-    int* par = parent + (size_t)p.c * g.NHW;
-    const int v = p.n * g.HW + y * g.W + j * 64 + lane;
-    if (lane == 0 && w) unite(par, v, v - 1);                           // runs were joined inside a word only
-    if (n && !(w && nwb)) unite(par, v, v - g.W);                       // with w and nw set the left neighbour unites with the row above
-    if (!n) {
-      if (nwb && !w) unite(par, v, v - g.W - 1);                        // with w set, nw is w's upper neighbour
-      if (neb && !e) unite(par, v, v - g.W + 1);                        // with e set, ne is e's upper neighbour
-    }
-  }
-}
-
 // a thread per word of the slices n >= 1
-__global__ __launch_bounds__(NT) void vol_across_kernel(const u64* __restrict__ bits, int C, VGeo g, int full, int* __restrict__ parent) {
-  const size_t total = (size_t)C * g.words;
+__global__ __launch_bounds__(NT) void vol_across_kernel(const u64* __restrict__ bits, int C, BitGeo g, int full, int* __restrict__ parent) {
+  const size_t total = (size_t)C * g.words();
   for (size_t it = (size_t)blockIdx.x * NT + threadIdx.x; it < total; it += (size_t)gridDim.x * NT) {
     const u64 c = bits[it];
     if (!c) continue;
     const Place p = place(it, g);
     if (p.n == 0) continue;
-    const u64* up = bits + ((size_t)p.c * g.N + p.n - 1) * g.H * g.W64;
-    int* par = parent + (size_t)p.c * g.NHW;
+    const u64* up = bits + ((size_t)p.s * g.D + p.n - 1) * g.H * g.W64;
+    int* par = parent + (size_t)p.s * g.DHW;
     const int a0 = p.n * g.HW + p.y * g.W + p.j * 64;
     if (!full) {
-      unite_runs(par, c & rds(up, p.y, p.j, g), a0, -g.HW);
+      unite_runs(par, c & rdw(up, p.y, p.j, g), a0, -g.HW);
       continue;
     }
     for (int dy = -1; dy <= 1; ++dy) {
-      const u64 w = rds(up, p.y + dy, p.j, g), wl = rds(up, p.y + dy, p.j - 1, g), wr = rds(up, p.y + dy, p.j + 1, g);
+      const u64 w = rdw(up, p.y + dy, p.j, g), wl = rdw(up, p.y + dy, p.j - 1, g), wr = rdw(up, p.y + dy, p.j + 1, g);
       const int off = -g.HW + dy * g.W;
       unite_runs(par, c & w, a0, off);
       // a bit whose own source column is set was united above, and that source is its row neighbours' neighbour: the shifted words skip it
       unite_runs(par, c & ((w >> 1) | (wr << 63)) & ~w, a0, off + 1);   // source column x + 1
       unite_runs(par, c & ((w << 1) | (wl >> 63)) & ~w, a0, off - 1);   // source column x - 1
     }
-  }
-}
-
-__global__ __launch_bounds__(NT) void vol_flatten_kernel(const u64* __restrict__ bits, int C, VGeo g, int* __restrict__ parent) {
-  const int lane = threadIdx.x & 63;
-  const size_t nw = (size_t)gridDim.x * WAVES, total = (size_t)C * g.words;
-  for (size_t it = (size_t)blockIdx.x * WAVES + (threadIdx.x >> 6); it < total; it += nw) {
-    const u64 c = bits[it];
-    if (!c || !((c >> lane) & 1ull)) continue;
-    if (lane && ((c >> (lane - 1)) & 1ull)) continue;           // not a run start: its parent is the run start since init, one hop from the root
-    const Place p = place(it, g);
-    int* par = parent + (size_t)p.c * g.NHW;
-    const int v = p.n * g.HW + p.y * g.W + p.j * 64 + lane;
-    // the forest is final (the merges have completed): every value a concurrent flatten writes is the root, a valid ancestor
-    const int r = find_root(par, v);
-    if (r != v) par[v] = r;
-  }
-}
-
-__global__ __launch_bounds__(NT) void vol_labels_kernel(const u64* __restrict__ bits, int C, VGeo g, const int* __restrict__ parent,
-                                                        int* __restrict__ labels) {
-  const int lane = threadIdx.x & 63;
-  const size_t nw = (size_t)gridDim.x * WAVES, total = (size_t)C * g.words;
-  for (size_t it = (size_t)blockIdx.x * WAVES + (threadIdx.x >> 6); it < total; it += nw) {
-    const Place p = place(it, g);
-    const int x = p.j * 64 + lane;
-    if (x >= g.W) continue;
-    const u64 c = bits[it];
-    const size_t base = (size_t)p.c * g.NHW, o = base + (size_t)(p.n * g.HW + p.y * g.W + x);
-    labels[o] = ((c >> lane) & 1ull) ? parent[base + parent[o]] + 1 : 0;      // voxel -> run start -> root (a root points at itself)
   }
 }
 
@@ -227,15 +85,15 @@ __device__ __forceinline__ int wave_sum(int v) { for (int o = 32; o > 0; o >>= 1
 __device__ __forceinline__ int wave_min(int v) { for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o)); return v; }
 __device__ __forceinline__ int wave_max(int v) { for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o)); return v; }
 
-__global__ __launch_bounds__(NT) void vol_count_kernel(const u64* __restrict__ bits, int C, VGeo g, const int* __restrict__ parent, int* __restrict__ vox,
+__global__ __launch_bounds__(NT) void vol_count_kernel(const u64* __restrict__ bits, int C, BitGeo g, const int* __restrict__ parent, int* __restrict__ vox,
                                                        int* __restrict__ zmax, int* __restrict__ list, int* __restrict__ nroots, int cap) {
   const int lane = threadIdx.x & 63;
-  const size_t total = (size_t)C * g.words;
+  const size_t total = (size_t)C * g.words();
   for (size_t first = (size_t)blockIdx.x * NT; first < total; first += (size_t)gridDim.x * NT) {      // block-uniform
     const size_t it = first + threadIdx.x;
     u64 c = it < total ? bits[it] : 0ull;
     const Place p = place(it < total ? it : 0, g);
-    const size_t base = (size_t)p.c * g.NHW;
+    const size_t base = (size_t)p.s * g.DHW;
     const int a0 = p.n * g.HW + p.y * g.W + p.j * 64;
     while (__any(c != 0ull)) {                                          // every round clears one run in every lane that has one
       const bool has = c != 0ull;
@@ -247,8 +105,8 @@ __global__ __launch_bounds__(NT) void vol_count_kernel(const u64* __restrict__ b
         const int r = parent[base + a0 + s];
         key = (long long)(base + r);
         if (r == a0 + s) {
-          const int slot = atomicAdd(nroots + p.c, 1);
-          if (slot < cap) list[(size_t)p.c * cap + slot] = r;
+          const int slot = atomicAdd(nroots + p.s, 1);
+          if (slot < cap) list[(size_t)p.s * cap + slot] = r;
         }
         c &= ~runmask(s, len);
       }
@@ -260,7 +118,7 @@ __global__ __launch_bounds__(NT) void vol_count_kernel(const u64* __restrict__ b
         const int sum = wave_sum(mine ? len : 0), zhi = wave_max(mine ? p.n : 0);
         if (lane == leader) {
           atomicAdd(vox + k, sum);
-          if (zhi > (int)((k % g.NHW) / g.HW)) atomicMax(zmax + k, zhi);      // zmax[root] starts at the root's slice z0: that slice needs no atomic
+          if (zhi > (int)((k % g.DHW) / g.HW)) atomicMax(zmax + k, zhi);      // zmax[root] starts at the root's slice z0: that slice needs no atomic
         }
         pending &= ~__ballot(mine);
       }
@@ -273,7 +131,7 @@ __global__ __launch_bounds__(NT) void vol_count_kernel(const u64* __restrict__ b
 // and the ranking cover the kept lesions.  key = vox << 32 | (2^31 - 1 - first voxel): the largest key is the largest lesion, ties to the earliest
 // first voxel; keys are distinct and non-zero.  Round i takes the largest key below round i - 1's.  rank: the 32 ranked roots, -1 = none.
 __global__ __launch_bounds__(SEL_NT) void vol_select_kernel(const int* __restrict__ vox, const int* __restrict__ zmax, const int* __restrict__ list,
-                                                            const int* __restrict__ nroots, VGeo g, int cap, int keep, int min_voxels, int min_slices,
+                                                            const int* __restrict__ nroots, BitGeo g, int cap, int keep, int min_voxels, int min_slices,
                                                             int* __restrict__ thr_out, int* __restrict__ rank, int* __restrict__ nles,
                                                             int* __restrict__ top) {
   __shared__ u64 red[SEL_NT];
@@ -281,8 +139,8 @@ __global__ __launch_bounds__(SEL_NT) void vol_select_kernel(const int* __restric
   const int tid = threadIdx.x, bd = blockDim.x;
   const size_t ch = blockIdx.x;
   const int n = min(max(nroots[ch], 0), cap);
-  const int* vx = vox + ch * g.NHW;
-  const int* zm = zmax + ch * g.NHW;
+  const int* vx = vox + ch * g.DHW;
+  const int* zm = zmax + ch * g.DHW;
   const int* ls = list + ch * (size_t)cap;
   // workgroup-uniform reductions over red
   auto reduce_sum = [&](int mine) -> int {
@@ -361,7 +219,7 @@ __global__ __launch_bounds__(SEL_NT) void vol_select_kernel(const int* __restric
 
 // grid (x, C): the runs of a channel's ranked lesions reduce their bounding box into top and add to profile[rank][slice]; runs of one lesion and
 // slice are reduced inside the wave first, as in vol_count_kernel
-__global__ __launch_bounds__(NT) void vol_extent_kernel(const u64* __restrict__ bits, VGeo g, const int* __restrict__ parent, const int* __restrict__ rank,
+__global__ __launch_bounds__(NT) void vol_extent_kernel(const u64* __restrict__ bits, BitGeo g, const int* __restrict__ parent, const int* __restrict__ rank,
                                                         int* __restrict__ top, int* __restrict__ profile) {
   __shared__ int rr[TOPL];
   const int lane = threadIdx.x & 63;
@@ -369,12 +227,12 @@ __global__ __launch_bounds__(NT) void vol_extent_kernel(const u64* __restrict__ 
   if (threadIdx.x < TOPL) rr[threadIdx.x] = rank[ch * TOPL + threadIdx.x];
   __syncthreads();
   if (rr[0] < 0) return;                                       // no lesion in this channel (workgroup-uniform, after the only barrier)
-  const u64* vol = bits + ch * g.words;
-  const int* par = parent + ch * g.NHW;
-  for (size_t first = (size_t)blockIdx.x * NT; first < g.words; first += (size_t)gridDim.x * NT) {   // block-uniform
+  const u64* vol = bits + ch * g.words();
+  const int* par = parent + ch * g.DHW;
+  for (size_t first = (size_t)blockIdx.x * NT; first < g.words(); first += (size_t)gridDim.x * NT) {   // block-uniform
     const size_t it = first + threadIdx.x;
-    u64 c = it < g.words ? vol[it] : 0ull;
-    const Place p = place(it < g.words ? it : 0, g);           // p.c == 0
+    u64 c = it < g.words() ? vol[it] : 0ull;
+    const Place p = place(it < g.words() ? it : 0, g);           // p.s == 0
     const int a0 = p.n * g.HW + p.y * g.W + p.j * 64;
     while (__any(c != 0ull)) {
       int key = -1, len = 0, x0 = 0;                           // key = rank * N + slice of a run of a ranked lesion
@@ -384,7 +242,7 @@ __global__ __launch_bounds__(NT) void vol_extent_kernel(const u64* __restrict__ 
         x0 = p.j * 64 + s;
         const int r = par[a0 + s];
         for (int i = 0; i < TOPL; ++i)
-          if (rr[i] == r) { key = i * g.N + p.n; break; }
+          if (rr[i] == r) { key = i * g.D + p.n; break; }
         c &= ~runmask(s, len);
       }
       const bool has = key >= 0;
@@ -397,7 +255,7 @@ __global__ __launch_bounds__(NT) void vol_extent_kernel(const u64* __restrict__ 
           const int y0 = wave_min(mine ? p.y : g.H), y1 = wave_max(mine ? p.y : -1);
           const int xa = wave_min(mine ? x0 : g.W), xb = wave_max(mine ? x0 + len - 1 : -1);
           if (lane == leader) {
-            int* t = top + (ch * TOPL + k / g.N) * LCOL;
+            int* t = top + (ch * TOPL + k / g.D) * LCOL;
             atomicMin(t + 4, y0);
             atomicMax(t + 5, y1);
             atomicMin(t + 6, xa);
@@ -406,7 +264,7 @@ __global__ __launch_bounds__(NT) void vol_extent_kernel(const u64* __restrict__ 
         }
         if (profile) {
           const int sum = wave_sum(mine ? len : 0);
-          if (lane == leader) atomicAdd(profile + ch * TOPL * g.N + k, sum);      // (ch * 32 + rank) * N + slice
+          if (lane == leader) atomicAdd(profile + ch * TOPL * g.D + k, sum);      // (ch * 32 + rank) * N + slice
         }
         pending &= ~__ballot(mine);
       }
@@ -414,30 +272,7 @@ __global__ __launch_bounds__(NT) void vol_extent_kernel(const u64* __restrict__ 
   }
 }
 
-__global__ __launch_bounds__(NT) void vol_keep_kernel(const u64* __restrict__ bits, int C, VGeo g, const int* __restrict__ parent, const int* __restrict__ vox,
-                                                      const int* __restrict__ zmax, const int* __restrict__ thr, int min_slices, u64* __restrict__ kept) {
-  const size_t total = (size_t)C * g.words;
-  for (size_t it = (size_t)blockIdx.x * NT + threadIdx.x; it < total; it += (size_t)gridDim.x * NT) {
-    u64 c = bits[it], o = 0ull;
-    if (c) {
-      const Place p = place(it, g);
-      const size_t base = (size_t)p.c * g.NHW;
-      const int a0 = p.n * g.HW + p.y * g.W + p.j * 64, th = thr[p.c];
-      while (c) {
-        const int s = ctz64(c), len = runlen(c, s);
-        const u64 m = runmask(s, len);
-        const int r = parent[base + a0 + s];
-        if (vox[base + r] >= th && zmax[base + r] - r / g.HW + 1 >= min_slices) o |= m;
-        c &= ~m;
-      }
-    }
-    kept[it] = o;
-  }
-}
-
 namespace {
-
-size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 struct VScratch {
   int *parent, *vox, *zmax, *list, *nroots, *thr, *rank;
@@ -450,40 +285,29 @@ VScratch carve(void* base, size_t C, int N, int H, int W) {
   VScratch s;
   const size_t NHW = (size_t)N * H * W, W64 = ((size_t)W + 63) / 64;
   s.cap = (int)((size_t)N * (((size_t)H + 1) / 2) * (((size_t)W + 1) / 2));
-  const uintptr_t p = (uintptr_t)base;      // integer arithmetic: the size query carves from a null base
-  size_t o = 0;
-  s.parent = (int*)(p + o); o += al256(C * NHW * sizeof(int));
-  s.vox = (int*)(p + o); o += al256(C * NHW * sizeof(int));
-  s.zmax = (int*)(p + o); o += al256(C * NHW * sizeof(int));
-  s.list = (int*)(p + o); o += al256(C * (size_t)s.cap * sizeof(int));
-  s.nroots = (int*)(p + o); o += al256(C * sizeof(int));
-  s.thr = (int*)(p + o); o += al256(C * sizeof(int));
-  s.rank = (int*)(p + o); o += al256(C * TOPL * sizeof(int));
-  s.a = (u64*)(p + o); o += al256(C * N * H * W64 * sizeof(u64));
-  s.b = (u64*)(p + o); o += al256(C * N * H * W64 * sizeof(u64));
-  s.bytes = o;
+  Carver cv(base);
+  s.parent = cv.take<int>(C * NHW);
+  s.vox = cv.take<int>(C * NHW);
+  s.zmax = cv.take<int>(C * NHW);
+  s.list = cv.take<int>(C * (size_t)s.cap);
+  s.nroots = cv.take<int>(C);
+  s.thr = cv.take<int>(C);
+  s.rank = cv.take<int>(C * TOPL);
+  s.a = cv.take<u64>(C * N * H * W64);
+  s.b = cv.take<u64>(C * N * H * W64);
+  s.bytes = cv.used;
   return s;
 }
 
-VGeo vgeo(int N, int H, int W) {
-  const int W64 = (W + 63) / 64;
-  return VGeo{N, H, W, W64, H * W, N * H * W, (size_t)N * H * W64};
-}
-
-unsigned wave_grid(size_t words) { return (unsigned)std::min<size_t>((words + WAVES - 1) / WAVES, MAX_GRID); }
-unsigned word_grid(size_t words) { return (unsigned)std::min<size_t>((words + NT - 1) / NT, MAX_GRID); }
-
 // pack and label; with `rank` also count and select: the threshold, the count and the ranking
-hipError_t label_and_rank(const float* stack, const VGeo& g, int C, int full, bool rank, int keep, int min_voxels, int min_slices, const VScratch& s,
+hipError_t label_and_rank(const float* stack, const BitGeo& g, int C, int full, bool rank, int keep, int min_voxels, int min_slices, const VScratch& s,
                           int* nles, int* top, hipStream_t st) {
-  const size_t total = (size_t)C * g.words;
-  const unsigned gw = wave_grid(total), gt = word_grid(total);
-  const int vec = (C == 4 && ((uintptr_t)stack & 15) == 0) ? 1 : 0;
-  hipLaunchKernelGGL(vol_pack_kernel, dim3(wave_grid(g.words)), dim3(NT), 0, st, stack, g, C, s.a, vec);
-  hipLaunchKernelGGL(vol_init_kernel, dim3(gw), dim3(NT), 0, st, s.a, C, g, s.parent, s.vox, s.zmax);
-  hipLaunchKernelGGL(vol_merge_kernel, dim3(gw), dim3(NT), 0, st, s.a, C, g, s.parent);
-  if (g.N > 1) hipLaunchKernelGGL(vol_across_kernel, dim3(gt), dim3(NT), 0, st, s.a, C, g, full, s.parent);
-  hipLaunchKernelGGL(vol_flatten_kernel, dim3(gw), dim3(NT), 0, st, s.a, C, g, s.parent);
+  const unsigned gt = item_grid((size_t)C * g.words());
+  launch_bits_pack(stack, g.D, g, C, 1, g.D, s.a, st);
+  launch_ccl_init(s.a, C, g, 0, s.parent, s.vox, s.zmax, st);
+  launch_ccl_merge(s.a, C, g, 0, 1, s.parent, st);
+  if (g.D > 1) hipLaunchKernelGGL(vol_across_kernel, dim3(gt), dim3(NT), 0, st, s.a, C, g, full, s.parent);
+  launch_ccl_flatten(s.a, C, g, 0, s.parent, st);
   if (!rank) return hipSuccess;                                 // labels only
   hipError_t e = hipMemsetAsync(s.nroots, 0, (size_t)C * sizeof(int), st);
   if (e != hipSuccess) return e;
@@ -493,12 +317,12 @@ hipError_t label_and_rank(const float* stack, const VGeo& g, int C, int full, bo
   return hipSuccess;
 }
 
-hipError_t extents(const VGeo& g, int C, const VScratch& s, int* top, int* profile, hipStream_t st) {
+hipError_t extents(const BitGeo& g, int C, const VScratch& s, int* top, int* profile, hipStream_t st) {
   if (profile) {
-    hipError_t e = hipMemsetAsync(profile, 0, (size_t)C * TOPL * g.N * sizeof(int), st);
+    hipError_t e = hipMemsetAsync(profile, 0, (size_t)C * TOPL * g.D * sizeof(int), st);
     if (e != hipSuccess) return e;
   }
-  const unsigned gx = (unsigned)std::min<size_t>((g.words + NT - 1) / NT, 1u << 16);
+  const unsigned gx = (unsigned)std::min<size_t>((g.words() + NT - 1) / NT, 1u << 16);
   hipLaunchKernelGGL(vol_extent_kernel, dim3(gx, C), dim3(NT), 0, st, s.a, g, s.parent, s.rank, top, profile);
   return hipSuccess;
 }
@@ -509,11 +333,11 @@ size_t lesions_scratch_bytes(size_t channels, int N, int H, int W) { return carv
 
 hipError_t launch_volume_components(const float* stack, int N, int H, int W, int C, int full, void* scratch, int* labels, int* nles, int* top,
                                     int* profile, hipStream_t st) {
-  const VGeo g = vgeo(N, H, W);
+  const BitGeo g = bit_geo(N, H, W);
   const VScratch s = carve(scratch, C, N, H, W);
   hipError_t e = label_and_rank(stack, g, C, full, nles || top || profile, 0, 0, 1, s, nles, top, st);
   if (e != hipSuccess) return e;
-  if (labels) hipLaunchKernelGGL(vol_labels_kernel, dim3(wave_grid((size_t)C * g.words)), dim3(NT), 0, st, s.a, C, g, s.parent, labels);
+  if (labels) launch_ccl_labels(s.a, C, g, s.parent, labels, st);
   if (top || profile) {
     e = extents(g, C, s, top, profile, st);
     if (e != hipSuccess) return e;
@@ -523,7 +347,7 @@ hipError_t launch_volume_components(const float* stack, int N, int H, int W, int
 
 hipError_t launch_volume_cleanup(const float* stack, int N, int H, int W, int C, int full, int keep, int min_voxels, int min_slices, void* scratch,
                                  float* out, int* nles, int* top, hipStream_t st) {
-  const VGeo g = vgeo(N, H, W);
+  const BitGeo g = bit_geo(N, H, W);
   const VScratch s = carve(scratch, C, N, H, W);
   hipError_t e = label_and_rank(stack, g, C, full, true, keep, min_voxels, min_slices, s, nles, top, st);
   if (e != hipSuccess) return e;
@@ -531,10 +355,8 @@ hipError_t launch_volume_cleanup(const float* stack, int N, int H, int W, int C,
     e = extents(g, C, s, top, nullptr, st);
     if (e != hipSuccess) return e;
   }
-  const size_t total = (size_t)C * g.words;
-  hipLaunchKernelGGL(vol_keep_kernel, dim3(word_grid(total)), dim3(NT), 0, st, s.a, C, g, s.parent, s.vox, s.zmax, s.thr, min_slices, s.b);
-  const int vec = (C == 4 && ((uintptr_t)out & 15) == 0) ? 1 : 0;
-  hipLaunchKernelGGL(vol_unpack_kernel, dim3(wave_grid(g.words)), dim3(NT), 0, st, s.b, g, C, out, vec);
+  launch_ccl_keep(s.a, C, g, s.parent, s.vox, s.zmax, s.thr, min_slices, s.b, st);
+  launch_bits_unpack(s.b, g.D, g, C, 1, g.D, out, st);
   return hipGetLastError();
 }
 

@@ -367,6 +367,65 @@ def test_outputs_stay_inside_their_extent_and_refused_calls_launch_nothing():
     assert torch.equal(d, before)
 
 
+# ---- 10. the scratch is work space only: no result depends on what it held (the labelling initialises its counters at run starts only)
+SCRATCH_FILLS = (0x00, 0xFF, 0x55)
+
+
+@functools.lru_cache(maxsize=None)
+def density_stack(ch):
+    """[2, 9, 65, ch]: seeded random planes at densities 0.45 / 0.03 / 0.9 (/ 0.45); W crosses one word boundary.  Read-only."""
+    rng = np.random.RandomState(965 + ch)
+    st = np.stack([rng.rand(2, 9, 65) < p for p in (0.45, 0.03, 0.9, 0.45)[:ch]], axis=-1).astype(np.float32)
+    st.setflags(write=False)
+    return st
+
+
+@pytest.mark.parametrize('ch', [3, 4])                                  # the scalar pack / unpack path, the float4 one
+def test_stack_cleanup_does_not_depend_on_the_scratch(ch):
+    st = density_stack(ch)
+    n, h, w, _ = st.shape
+    d = dev(st)
+    lib = L.lib()
+    need = int(lib.octseg_components_scratch_bytes(n * ch, h, w))
+    got = []
+    for fill in SCRATCH_FILLS:
+        scratch = torch.full((need,), fill, dtype=torch.uint8, device='cuda')
+        out = torch.full((n, h, w, ch), 7.0, dtype=torch.float32, device='cuda')
+        ncomp = torch.full((n * ch,), 7, dtype=torch.int32, device='cuda')
+        top = torch.full((n * ch, 8, 6), 7, dtype=torch.int32, device='cuda')
+        # smoothing, the labelling with the filter, and the labelling of the complement for the fill: two labelling passes over one scratch
+        L.check(lib.octseg_stack_cleanup(L.ptr(d), n, h, w, ch, 2, 3, 2, 1, L.ptr(scratch), need, L.ptr(out), L.ptr(ncomp), L.ptr(top),
+                                         L.stream_ptr()))
+        got.append((host(out), host(ncomp).reshape(n, ch), host(top).reshape(n, ch, 8, 6)))
+    want_n, want_top = R.table_stack(st, lambda p: R.kept_table(R.smooth(p, 2), 3, 2))
+    want = (R.per_plane(st, lambda p: R.clean(p, 2, 3, 2, True)), want_n, want_top)
+    for fill, g in zip(SCRATCH_FILLS, got):
+        for name, a, b, first in zip(('out', 'ncomp', 'top'), g, want, got[0]):
+            assert np.array_equal(a, first), f'{name} differs between scratch fills 0x00 and {fill:#04x}'
+            assert np.array_equal(a, b), f'{name} differs from the reference with scratch fill {fill:#04x}'
+
+
+def test_stack_components_do_not_depend_on_the_scratch():
+    st = density_stack(3)
+    n, h, w, ch = st.shape
+    d = dev(st)
+    lib = L.lib()
+    need = int(lib.octseg_components_scratch_bytes(n * ch, h, w))
+    got = []
+    for fill in SCRATCH_FILLS:
+        scratch = torch.full((need,), fill, dtype=torch.uint8, device='cuda')
+        labels = torch.full((n * ch, h, w), 7, dtype=torch.int32, device='cuda')
+        ncomp = torch.full((n * ch,), 7, dtype=torch.int32, device='cuda')
+        top = torch.full((n * ch, 8, 6), 7, dtype=torch.int32, device='cuda')
+        L.check(lib.octseg_stack_components(L.ptr(d), n, h, w, ch, L.ptr(scratch), need, L.ptr(labels), L.ptr(ncomp), L.ptr(top), L.stream_ptr()))
+        got.append((host(labels).reshape(n, ch, h, w), host(ncomp).reshape(n, ch), host(top).reshape(n, ch, 8, 6)))
+    want = (R.label_stack(st),) + R.table_stack(st)
+    for fill, g in zip(SCRATCH_FILLS, got):
+        for name, a, b, first in zip(('labels', 'ncomp', 'top'), g, want, got[0]):
+            assert np.array_equal(a, first), f'{name} differs between scratch fills 0x00 and {fill:#04x}'
+            assert np.array_equal(a, b), f'{name} differs from the reference with scratch fill {fill:#04x}'
+
+
 def test_wrappers_refuse_wrong_dtype_rank_and_channels():
     for bad in (torch.zeros((1, 4, 4, 4), dtype=torch.float64, device='cuda'), torch.zeros((4, 4, 4), device='cuda'),
                 torch.zeros((1, 0, 4, 4), device='cuda'), torch.zeros((1, 4, 4, 17), device='cuda')):

@@ -317,6 +317,44 @@ def test_outputs_stay_inside_their_extent_and_refused_calls_launch_nothing():
     assert torch.equal(d, before)                                        # the input stack is never modified
 
 
+# ---- 7b. the scratch is work space only: no result depends on what it held (the labelling initialises its counters at run starts only)
+SCRATCH_FILLS = (0x00, 0xFF, 0x55)
+
+
+def _same_for_every_fill(got, want, names, what):
+    for fill, g in zip(SCRATCH_FILLS, got):
+        for name, a, b, first in zip(names, g, want, got[0]):
+            assert np.array_equal(a, first), f'{what}: {name} differs between scratch fills 0x00 and {fill:#04x}'
+            assert np.array_equal(a, b), f'{what}: {name} differs from the reference with scratch fill {fill:#04x}'
+
+
+@pytest.mark.parametrize('across', [0, 1])
+def test_volume_calls_do_not_depend_on_the_scratch(across):
+    n, h, w, c = 3, 9, 65, 3
+    st = seeded_stack(n, h, w, c)
+    d = dev(st)
+    lib = L.lib()
+    need = int(lib.octseg_lesions_scratch_bytes(c, n, h, w))
+    s = L.stream_ptr()
+    comps, cleans = [], []
+    for fill in SCRATCH_FILLS:
+        labels = torch.full((c, n, h, w), 7, dtype=torch.int32, device='cuda')
+        nles = torch.full((c,), 7, dtype=torch.int32, device='cuda')
+        top = torch.full((c, 32, 8), 7, dtype=torch.int32, device='cuda')
+        prof = torch.full((c, 32, n), 7, dtype=torch.int32, device='cuda')
+        out = torch.full((n, h, w, c), 7.0, dtype=torch.float32, device='cuda')
+        scratch = torch.full((need,), fill, dtype=torch.uint8, device='cuda')
+        L.check(lib.octseg_volume_components(L.ptr(d), n, h, w, c, across, L.ptr(scratch), need, L.ptr(labels), L.ptr(nles), L.ptr(top), L.ptr(prof), s))
+        comps.append((host(labels), host(nles), host(top), host(prof)))
+        scratch.fill_(fill)
+        L.check(lib.octseg_volume_cleanup(L.ptr(d), n, h, w, c, across, 2, 0, 2, L.ptr(scratch), need, L.ptr(out), L.ptr(nles), L.ptr(top), s))
+        cleans.append((host(out), host(nles), host(top)))
+    name = ACROSS[across]
+    _same_for_every_fill(comps, (R.label_stack(st, name),) + tuple(R.table_stack(st, name)), ('labels', 'nles', 'top', 'profile'), 'volume_components')
+    kept = R.clean_stack(st, 2, 0, 2, name)
+    _same_for_every_fill(cleans, (kept,) + tuple(R.table_stack(kept, name)[:2]), ('out', 'nles', 'top'), 'volume_cleanup')
+
+
 def test_wrappers_refuse_wrong_dtype_rank_and_channels():
     for bad in (torch.zeros((2, 4, 4, 4), dtype=torch.float64, device='cuda'), torch.zeros((4, 4, 4), device='cuda'),
                 torch.zeros((2, 0, 4, 4), device='cuda'), torch.zeros((2, 4, 4, 17), device='cuda')):

@@ -28,11 +28,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 
+if os.environ.get('OCTSEG_LIB'):   # an experimental build of the library (timing experiments)
+    from oct_segmentation_amd import _lib as _L
+    _L.LIB_PATH = os.path.abspath(os.environ['OCTSEG_LIB'])
+
 N, SIZE, CHANNELS = 186, 1000, 4
 WARMUP = 3
 WORKERS = 16
-KERNELS = ('pack_kernel', 'morph_kernel', 'init_kernel', 'merge_kernel', 'flatten_kernel', 'area_kernel', 'select_kernel', 'keep_kernel',
-           'border_kernel', 'fill_kernel', 'unpack_kernel')
+KERNELS = ('bits_pack_kernel', 'morph_kernel', 'ccl_init_kernel', 'ccl_merge_kernel', 'ccl_flatten_kernel', 'area_kernel', 'select_kernel',
+           'ccl_keep_kernel', 'border_kernel', 'fill_kernel', 'bits_unpack_kernel')      # ccl_*: launched by the labelling and by the hole fill
 
 
 def _need_gpu():
@@ -160,7 +164,7 @@ def run_record(args):
     launches = {k: 0 for k in KERNELS}
     for name, start, end in rows:
         for k in KERNELS:
-            if re.search(r'(^|[^a-z_])' + k + r'\b', name):               # pack_kernel must not take unpack_kernel's launches
+            if re.search(r'(^|[^a-z_])' + k + r'\b', name):               # a name must not take the launches of one it is the tail of
                 total[k] += (end - start) / 1e3
                 launches[k] += 1
     calls = args.reps + WARMUP

@@ -30,12 +30,16 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 
+if os.environ.get('OCTSEG_LIB'):   # an experimental build of the library (timing experiments)
+    from oct_segmentation_amd import _lib as _L
+    _L.LIB_PATH = os.path.abspath(os.environ['OCTSEG_LIB'])
+
 N, SIZE, CHANNELS = 186, 750, 4
 HBM_ACHIEVABLE_TBS = 6.3
 WARMUP, REPS = 3, 20
 WORKERS = 16
 NONE = 0x7fffffff
-KERNELS = ('dist_pack_kernel', 'dist_unpack_kernel', 'dist_part_kernel', 'dist_column_kernel', 'dist_map_kernel', 'dist_count_kernel',
+KERNELS = ('bits_pack_kernel', 'bits_unpack_kernel', 'dist_part_kernel', 'dist_column_kernel', 'dist_map_kernel', 'dist_count_kernel',
            'dist_query_kernel')
 
 

@@ -31,12 +31,16 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 sys.path.insert(0, os.path.join(ROOT, 'tools'))
 
+if os.environ.get('OCTSEG_LIB'):   # an experimental build of the library (timing experiments)
+    from oct_segmentation_amd import _lib as _L
+    _L.LIB_PATH = os.path.abspath(os.environ['OCTSEG_LIB'])
+
 N, SIZE, CHANNELS = 186, 750, 4
 WARMUP = 3
 WORKERS = 16
 ACROSS = 'overlap'
-KERNELS = ('vol_pack_kernel', 'vol_init_kernel', 'vol_merge_kernel', 'vol_across_kernel', 'vol_flatten_kernel', 'vol_count_kernel',
-           'vol_select_kernel', 'vol_extent_kernel', 'vol_keep_kernel', 'vol_unpack_kernel', 'vol_labels_kernel')
+KERNELS = ('bits_pack_kernel', 'ccl_init_kernel', 'ccl_merge_kernel', 'vol_across_kernel', 'ccl_flatten_kernel', 'vol_count_kernel',
+           'vol_select_kernel', 'vol_extent_kernel', 'ccl_keep_kernel', 'bits_unpack_kernel', 'ccl_labels_kernel')
 
 
 def _need_gpu():

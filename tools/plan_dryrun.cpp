@@ -6,8 +6,8 @@
 // encoder pair at the smallest legal frame, the benchmark frame and a non-square one, in all three dtypes, with no kernel launched
 // (no GPU needed).  A subset of the plans is then driven through octseg_net_forward / _backward / _backward_sliced / octseg_optim_step and
 // the graph-captured eval forward, and the class-activation-map path (frozen forward, seeded backward, map launches) against tools/hip_host_stubs.cpp, a recording stand-in for the HIP runtime that checks every launch
-// geometry and every memset / copy range; the boundary-distance entry points (csrc/distance.hip) and the 3-D lesion entry points (csrc/lesions.hip) are driven the same way, from a 1 x 1 frame to
-// 4096 x 4096.  Exit code 0 = the sanitizers and the stubs saw nothing.
+// geometry and every memset / copy range; the boundary-distance entry points (csrc/distance.hip), the 3-D lesion entry points (csrc/lesions.hip) and the
+// mask clean-up entry points (csrc/components.hip) are driven the same way, from a 1 x 1 frame to the largest one each takes.  Exit code 0 = the sanitizers and the stubs saw nothing.
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -210,6 +210,63 @@ int exercise_lesions() {
     return 45;
   return 0;
 }
+
+// The mask clean-up entry points (csrc/components.hip over the shared kernels of csrc/bitplanes.hip, csrc/api.cpp) against the stubs: the scratch
+// carving, the memset of the component counters inside its range and every grid, from a single pixel to a frame just under 2^31 - 1 pixels;
+// every combination of outputs and of the smoothing, the filter and the fill; then what they must refuse.
+int exercise_components() {
+  char* base = (char*)(uintptr_t)0x400000000000ull;
+  auto carve = [&](size_t bytes) { char* r = base; base += (bytes + 4095) / 4096 * 4096 + 4096; dry_register_range(r, bytes); return r; };
+  const int shapes[][4] = {{1, 1, 1, 1}, {3, 97, 130, 5}, {186, 1000, 1000, 4}, {1, 46340, 46340, 1}};      // 46340^2 = 2^31 - 88048
+  for (auto& sh : shapes) {
+    dry_clear_ranges();
+    const int N = sh[0], H = sh[1], W = sh[2], C = sh[3];
+    const size_t need = octseg_components_scratch_bytes(N * C, H, W);
+    if (need == 0 || need <= octseg_components_scratch_bytes(1, H, W) - (N * C == 1)) return 50;
+    const size_t elems = (size_t)N * H * W * C;
+    float* a = (float*)carve(elems * 4);
+    float* out = (float*)carve(elems * 4);
+    int* labels = (int*)carve(elems * 4);
+    void* scratch = carve(need);
+    int* ncomp = (int*)carve((size_t)N * C * 4);
+    int* top = (int*)carve((size_t)N * C * 8 * 6 * 4);
+    void* st = (void*)(uintptr_t)0x5000;
+    for (int mask = 1; mask < 8; ++mask)            // labels, ncomp, top: each combination that asks for something
+      if (octseg_stack_components(a, N, H, W, C, scratch, need, mask & 1 ? labels : nullptr, mask & 2 ? ncomp : nullptr, mask & 4 ? top : nullptr, st) != 0) {
+        fprintf(stderr, "stack_components: %s\n", octseg_last_error());
+        return 51;
+      }
+    for (int smooth_k : {0, 1, 2, 7})
+      for (int filter = 0; filter < 3; ++filter)    // no filter, keep-largest, min_area
+        for (int fill = 0; fill < 2; ++fill)
+          for (int tables = 0; tables < 2; ++tables)
+            if (octseg_stack_cleanup(a, N, H, W, C, smooth_k, filter == 1 ? 3 : 0, filter == 2 ? 5 : 0, fill, scratch, need, out, tables ? ncomp : nullptr,
+                                     tables ? top : nullptr, st) != 0) {
+              fprintf(stderr, "stack_cleanup: %s\n", octseg_last_error());
+              return 52;
+            }
+    // refused before anything is enqueued
+    const unsigned long long before = dry_launches() + dry_memops();
+    if (octseg_stack_components(a, N, H, W, C, scratch, need - 1, labels, ncomp, top, st) == 0 ||
+        octseg_stack_components(a, N, H, W, C, nullptr, need, labels, ncomp, top, st) == 0 ||
+        octseg_stack_components(a, N, H, W, C, (char*)scratch + 4, need, labels, ncomp, top, st) == 0 ||
+        octseg_stack_components(a, N, H, W, 17, scratch, need, labels, ncomp, top, st) == 0 ||
+        octseg_stack_components(a, N, 0, W, C, scratch, need, labels, ncomp, top, st) == 0 ||
+        octseg_stack_components(a, N, H, W, C, scratch, need, nullptr, nullptr, nullptr, st) == 0 ||
+        octseg_stack_cleanup(a, N, H, W, C, 8, 3, 0, 1, scratch, need, out, ncomp, top, st) == 0 ||
+        octseg_stack_cleanup(a, N, H, W, C, -1, 3, 0, 1, scratch, need, out, ncomp, top, st) == 0 ||
+        octseg_stack_cleanup(a, N, H, W, C, 2, -1, 0, 1, scratch, need, out, ncomp, top, st) == 0 ||
+        octseg_stack_cleanup(a, N, H, W, C, 2, 3, -1, 1, scratch, need, out, ncomp, top, st) == 0 ||
+        octseg_stack_cleanup(a, N, H, W, C, 2, 3, 0, 1, scratch, need - 1, out, ncomp, top, st) == 0 ||
+        octseg_stack_cleanup(a, N, H, W, C, 2, 3, 0, 1, scratch, need, a, ncomp, top, st) == 0 ||
+        octseg_stack_cleanup(a, N, H, W, C, 2, 3, 0, 1, scratch, need, nullptr, ncomp, top, st) == 0)
+      return 53;
+    if (dry_launches() + dry_memops() != before) { fprintf(stderr, "a refused clean-up call enqueued work\n"); return 54; }
+  }
+  if (octseg_components_scratch_bytes(1, 46341, 46341) != 0 || octseg_components_scratch_bytes(0, 8, 8) != 0 || octseg_components_scratch_bytes(1, 8, 0) != 0)
+    return 55;
+  return 0;
+}
 }  // namespace
 
 int main() {
@@ -306,6 +363,7 @@ int main() {
   for (int dt = 0; dt < 3; ++dt) checksum += octseg_conv2d_scratch_bytes(dt, 2, 64, 64, 24, 40, 3, 3) + octseg_conv2d_scratch_bytes(dt, 1, 8, 8, 2048, 512, 1, 1);
   if (const int rc = exercise_distance()) { fprintf(stderr, "exercise_distance -> %d\n", rc); return rc; }
   if (const int rc = exercise_lesions()) { fprintf(stderr, "exercise_lesions -> %d\n", rc); return rc; }
+  if (const int rc = exercise_components()) { fprintf(stderr, "exercise_components -> %d\n", rc); return rc; }
   if (dry_errors() != 0) { fprintf(stderr, "%llu launch / memory-range violations\n", dry_errors()); return 8; }
   printf("plan_dryrun: %d plans built, %d of them run through forward / backward / optimizer with recording HIP stubs (%llu launches, %llu memory "
          "operations checked) under ASan + UBSan, checksum %llu, 0 errors, launch fingerprint %016llx\n", plans, executed, dry_launches(), dry_memops(), checksum,
