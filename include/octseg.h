@@ -50,6 +50,9 @@
  *   octseg_stack_components / octseg_stack_cleanup / octseg_components_scratch_bytes
  *                                      MaskProcessor.smooth_mask / .remove_artifacts, which process_pair runs over every annotated object
  *                                      (src/data/mask_processor.py:5-37, src/data/convert_int_to_cv.py:191-199)
+ *   octseg_stack_contour_counts / octseg_stack_contours / octseg_contours_scratch_bytes
+ *                                      (no reference counterpart) the crack contours of every mask plane: closed integer polygons along pixel
+ *                                      sides with holes, areas, perimeters, bounds and the owning component; not cv2.findContours
  *   octseg_stack_boundary / octseg_stack_distance / octseg_pair_distance_counts / _keys / _min / octseg_distance_scratch_bytes
  *                                      (no reference counterpart) exact squared Euclidean distance maps of the mask planes, the directed
  *                                      boundary-distance lists behind HD / HD95 / ASSD, the smallest distance between two classes
@@ -467,6 +470,51 @@ int octseg_stack_components(const float* stack, int N, int H, int W, int channel
                             int* top, void* stream);
 int octseg_stack_cleanup(const float* stack, int N, int H, int W, int channels, int smooth_k, int keep, int min_area, int fill_holes, void* scratch,
                          size_t scratch_bytes, float* out, int* ncomp, int* top, void* stream);
+
+/* Mask outlines (no reference counterpart: the reference draws skimage.measure.find_contours and ranks cv2.findContours, neither of which can
+ * be pinned here; what is restated are the definitions of DESIGN.md section 5n, pinned to scipy.ndimage.label and matplotlib.path by
+ * tests/contours_ref.py).  stack: device f32 [N][H][W][channels], any value != 0 is set, outside the frame is clear; a plane is one (slice,
+ * channel) pair.  Pixel (y, x) covers the square [x, x + 1] x [y, y + 1]; VERTICES are the lattice points (x, y), 0 <= x <= W, 0 <= y <= H.
+ *
+ * CRACK EDGES.  A set pixel (y, x) has a directed edge on each side whose neighbour is clear:
+ *   top    (y-1, x) clear: (x, y)     -> (x+1, y)    E = 0        bottom (y+1, x) clear: (x+1, y+1) -> (x, y+1)  W = 2
+ *   right  (y, x+1) clear: (x+1, y)   -> (x+1, y+1)  S = 1        left   (y, x-1) clear: (x, y+1)   -> (x, y)    N = 3
+ * so the set pixel is on the edge's right.  The id of an edge is ((y_s * (W + 1) + x_s) * 4 + dir) of its start vertex, unique in a plane.
+ * The SUCCESSOR of an edge is the edge that starts where it ends; at a vertex where two diagonal pixels are set and the other two clear there are
+ * two, and the successor is the one of the OTHER pixel: a turn from dir to (dir + 3) % 4.  The foreground is therefore 8-connected and the
+ * background 4-connected, as octseg_stack_components and the hole fill have it.  The edges of a plane fall into disjoint cycles: the CONTOURS.
+ * The LEADER of a contour is its edge with the smallest id: the E edge on top of the component's first pixel in raster order for an outer
+ * contour, an S edge for a hole.  The VERTEX LIST holds the start vertices of the edges whose predecessor has another direction, in cycle order
+ * from the leader's start vertex, closed implicitly; its length is even and at least 4.  Contours are ordered by plane (n * channels + c), then by
+ * leader id.  Not OpenCV's border following: those vertices are pixel centres in an order nothing here can pin.
+ *
+ * octseg_stack_contour_counts: counts int64 [N][channels][2], 8-byte aligned = the crack edges of the plane (field EDGES of octseg_stack_moments)
+ *   and the sum of its contours' vertex counts.  One memset and one pass over the stack; no scratch.
+ * octseg_stack_contours: traces every plane.
+ *   ncont    int32 [N][channels]: the contours of the plane;
+ *   table    int32 [contour_capacity][OCTSEG_CONTOUR_FIELDS], one row per contour of the call, rows beyond the total left alone:
+ *     0 plane (n * channels + c)    3 area   1/2 sum (x_i * y_i+1 - x_i+1 * y_i) over the vertex list, in pixels: > 0 for an outer contour (the
+ *     1 first vertex (row of           component's pixels with its holes filled), < 0 for a hole (minus its pixels); a plane's areas sum to its set pixels
+ *       `vertices`)                 4 edges  the cycle length = the crack perimeter      5..8 x0, y0, x1, y1  the vertex-lattice bounds
+ *     2 vertex count                9 label  1 + y * W + x of the first pixel in raster order of the 8-connected component that owns the set pixel
+ *                                            beside the leader: the contour's own component; for a hole, the component that encloses it
+ *   vertices int32 [vertex_capacity][2] = x, y, contour after contour.
+ *   overflow int32, cleared by the caller: set to 1 when the call has more edges than edge_capacity (then nothing is traced and ncont is zero),
+ *     more contours than contour_capacity or more vertices than vertex_capacity (then the rows and vertices that fit are complete and the others
+ *     are not stored): never a store past a buffer.  A call has at most edges / 4 contours and, by octseg_stack_contour_counts, known totals.
+ *   scratch: device, 8-byte aligned, scratch_bytes >= octseg_contours_scratch_bytes(N * channels, H, W, edge_capacity) (0 for what the call refuses).
+ * Everything is integer and every output is a function of the stack alone: two runs are bit-equal, and results EQUAL the restatement's.
+ * Enqueue only, nothing is allocated, the stack is not modified.  Null pointer, scratch too small or misaligned, counts not 8-byte aligned, a
+ * capacity <= 0 or >= 2^31: OCTSEG_BAD_ARG; N, H, W <= 0, channels outside 1..16, H * W >= 2^31 - 1, (H + 1) * (W + 1) >=
+ * OCTSEG_CONTOUR_MAX_VERTICES (an edge id fits 31 bits), N * channels * (H + 1) * (W / 64 + 1) >= 2^31: OCTSEG_BAD_SHAPE.  Every refusal happens
+ * before any HIP call: nothing is launched and no output is touched then. */
+#define OCTSEG_CONTOUR_FIELDS 10
+#define OCTSEG_CONTOUR_MAX_VERTICES (1 << 29)
+int octseg_stack_contour_counts(const float* stack, int N, int H, int W, int channels, long long* counts, void* stream);
+size_t octseg_contours_scratch_bytes(int planes, int H, int W, long long edge_capacity);
+int octseg_stack_contours(const float* stack, int N, int H, int W, int channels, void* scratch, size_t scratch_bytes, long long edge_capacity,
+                          long long contour_capacity, long long vertex_capacity, int* ncont, int* table, int* vertices, int* overflow,
+                          void* stream);
 
 /* Lesions in 3-D (no reference counterpart: the app's get_analysis groups slices by class presence only; DESIGN.md section 5j, pinned to
  * scipy.ndimage.label with an explicit 3 x 3 x 3 structure by tests/lesions_ref.py).  stack: device f32 [N][H][W][channels], any value != 0 is set.  A

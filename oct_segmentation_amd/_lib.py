@@ -156,6 +156,10 @@ SYMBOLS = {
     'octseg_components_scratch_bytes': (C.c_size_t, [C.c_int] * 3),
     'octseg_stack_components': (C.c_int, [_P] + [C.c_int] * 4 + [_P, C.c_size_t, _P, _P, _P, _P]),
     'octseg_stack_cleanup': (C.c_int, [_P] + [C.c_int] * 8 + [_P, C.c_size_t, _P, _P, _P, _P]),
+    # float32 mask stack -> crack-contour counts [N, C, 2]; -> per-contour table, vertex lists and labels (csrc/contours.hip)
+    'octseg_stack_contour_counts': (C.c_int, [_P] + [C.c_int] * 4 + [_P, _P]),
+    'octseg_contours_scratch_bytes': (C.c_size_t, [C.c_int] * 3 + [C.c_longlong]),
+    'octseg_stack_contours': (C.c_int, [_P] + [C.c_int] * 4 + [_P, C.c_size_t] + [C.c_longlong] * 3 + [_P] * 5),
     # float32 mask stack -> connected components across the slices (labels, count, the 32 largest with extents, per-slice profile) and the stack
     # filtered by voxel count, rank and slice span (csrc/lesions.hip)
     'octseg_lesions_scratch_bytes': (C.c_size_t, [C.c_int] * 4),

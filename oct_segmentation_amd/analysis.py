@@ -156,7 +156,7 @@ def build_analysis(counts, radii, h, w, image_names, ratio=None, masks=None):
     return data
 
 
-def analyze_stack(stack, image_names=None, ratio=None, thickness='radial', with_masks=False, clean=None):
+def analyze_stack(stack, image_names=None, ratio=None, thickness='radial', with_masks=False, clean=None, with_contours=False):
     """The app's ``get_analysis`` dict for a mask stack on the device.  NOTE: ``thickness_mean`` / ``thickness_min`` carry the median / min of
     upstream's RADIAL thickness function, ``calculate_object_thickness`` -- not of ``calculate_thickness_contour``, the call ``get_analysis``
     actually makes (analysis.py:202-207), whose result depends on ``cv2.findContours``' border-following order and vertex compression and has
@@ -167,7 +167,10 @@ def analyze_stack(stack, image_names=None, ratio=None, thickness='radial', with_
     ``with_masks=True`` also fills upstream's ``masks`` lists (base64 PNG of the 0 / 255 uint8 mask, analysis.py:208-211), which copies the
     present masks to the host; the default leaves the lists empty and the masks on the device.
     ``clean``: None (default, the stack is measured as it is), True or a dict of ``cleanup.clean_stack`` keywords: the stack goes through
-    ``clean_stack`` first (smoothing, keep-largest, hole fill) and the cleaned stack is what is measured and what ``with_masks`` encodes."""
+    ``clean_stack`` first (smoothing, keep-largest, hole fill) and the cleaned stack is what is measured and what ``with_masks`` encodes.
+    ``with_contours=True`` adds a ``contours`` list beside every class's ``masks``: per present slice the polygons of the mask
+    (``contours.Contours.polygons``: integer vertices on the pixel lattice, holes as ``interior`` rings), so that a viewer can draw outlines
+    without decoding a PNG; the dict gains ``contour_convention``.  Off by default: every other key is unchanged."""
     if thickness == 'contour':
         raise NotImplementedError("thickness='contour' (calculate_thickness_contour) needs cv2.findContours / contourArea / moments: its "
                                   'result depends on OpenCV\'s border-following order, tie-breaking among equal areas and '
@@ -188,4 +191,12 @@ def analyze_stack(stack, image_names=None, ratio=None, thickness='radial', with_
     if with_masks:
         def masks(idx, ch):
             return _mask_png_b64(((stack[idx, :, :, ch] != 0).to(torch.uint8) * 255).cpu().numpy())
-    return build_analysis(host[:, :, 0], host[:, :, 1:], h, w, image_names, ratio=ratio, masks=masks)
+    data = build_analysis(host[:, :, 0], host[:, :, 1:], h, w, image_names, ratio=ratio, masks=masks)
+    if with_contours:
+        from .contours import CONVENTION, trace_stack
+        polys = trace_stack(stack).polygons()
+        data['contour_convention'] = CONVENTION
+        for name, cid in CLASS_IDS.items():
+            obj = data['objects'][name]
+            obj['contours'] = [polys[idx][cid - 1] for idx in obj['slice']]
+    return data

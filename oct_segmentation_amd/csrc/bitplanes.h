@@ -35,7 +35,7 @@ struct BitGeo {
 void launch_bits_pack(const float* stack, int N, const BitGeo& g, int C, int stride_n, int stride_c, u64* bits, hipStream_t st);
 void launch_bits_unpack(const u64* bits, int N, const BitGeo& g, int C, int stride_n, int stride_c, float* out, hipStream_t st);
 // labelling of the S sets in `bits` (inv: of their complement inside the frame; conn8: 8- instead of 4-connected inside a plane).  init leaves
-// count = 0 (and zmax = its own plane, where zmax is not null) at every run start; merge unites inside every plane; the caller adds its own
+// count = 0 (and zmax = its own plane; each where the pointer is not null) at every run start; merge unites inside every plane; the caller adds its own
 // unites between planes; flatten leaves every pixel two hops from its root, the set's smallest index = its first pixel in raster order
 void launch_ccl_init(const u64* bits, int S, const BitGeo& g, int inv, int* parent, int* count, int* zmax, hipStream_t st);
 void launch_ccl_merge(const u64* bits, int S, const BitGeo& g, int inv, int conn8, int* parent, hipStream_t st);

@@ -91,7 +91,7 @@ __global__ __launch_bounds__(NT) void ccl_init_kernel(const u64* __restrict__ bi
     const size_t o = (size_t)p.s * g.DHW + (size_t)(v0 + lane);
     parent[o] = v0 + start;
     if (lane == start) {
-      count[o] = 0;
+      if (count) count[o] = 0;                                // (the contour tracer wants the labels only)
       if (zmax) zmax[o] = p.n;                                // the span of a component starts as its root's plane
     }
   }

@@ -397,6 +397,17 @@ hipError_t launch_stack_components(const float* stack, int N, int H, int W, int 
 hipError_t launch_stack_cleanup(const float* stack, int N, int H, int W, int C, int smooth_k, int keep, int min_area, int fill_holes, void* scratch,
                                 float* out, int* ncomp, int* top, hipStream_t st);
 
+// mask outlines (contours.hip): the crack contours of every (slice, channel) plane -- closed polygons along pixel sides, found by pointer jumping
+// over the edges' predecessor links, not by following them.  launch_stack_contour_counts: int64 [N][C][2] = edges, contour vertices, one memset and
+// one pass over the stack.  launch_stack_contours: ncont [N][C], table [contours][CONTOUR_FIELDS], vertices [.][2]; scratch:
+// contours_scratch_bytes(N * C, H, W, edge_capacity) device bytes; contours_rounds: the jump launches a call enqueues
+constexpr int CONTOUR_FIELDS = 10;
+size_t contours_scratch_bytes(size_t planes, int H, int W, size_t edge_capacity);
+int contours_rounds(int H, int W, size_t edge_capacity);
+hipError_t launch_stack_contour_counts(const float* stack, int N, int H, int W, int C, long long* counts, hipStream_t st);
+hipError_t launch_stack_contours(const float* stack, int N, int H, int W, int C, void* scratch, int edge_capacity, int contour_capacity,
+                                 int vertex_capacity, int* ncont, int* table, int* vertices, int* overflow, hipStream_t st);
+
 // lesions in 3-D (lesions.hip): the connected components of every channel's volume across the slices (8-connected inside a slice; between slices
 // the same pixel only, or with full != 0 the 3 x 3), the 32 largest with their extents, the per-slice area profile, and the voxel / rank / slice-span
 // filter.  scratch: lesions_scratch_bytes(C, N, H, W) device bytes; labels / nles / top / profile are optional (null = skipped)

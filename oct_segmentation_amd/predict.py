@@ -303,12 +303,21 @@ def _main_volume(cfg, device, dtypes, log):
         _save_lesions(res.stack, names, save_dir)
     if res.lumen is not None:
         _save_lumen(res.lumen, save_dir)
+    if bool(cfg.get('contours', False)):
+        _save_contours(res.stack, names, save_dir)
 
 
 def _save_lumen(report, save_dir):
     """``lumen=true``: ``{save_dir}/lumen.json``, ``shape.lumen_report`` of the stack that is rendered and measured (after ``clean``)."""
     with open(os.path.join(save_dir, 'lumen.json'), 'w') as f:
         json.dump(report, f)
+
+
+def _save_contours(stack, names, save_dir):
+    """``contours=true``: ``{save_dir}/contours.json``, ``contours.contour_report`` of the stack that is rendered and measured (after ``clean``)."""
+    from .contours import contour_report
+    with open(os.path.join(save_dir, 'contours.json'), 'w') as f:
+        json.dump(contour_report(stack, names), f)
 
 
 def _save_lesions(stack, names, save_dir):
@@ -384,6 +393,8 @@ def main(argv=None):
     ``lumen`` (default false): also write ``{save_dir}/lumen.json``, the lumen report of the same stack (``shape.lumen_report``: lumen area and
     the diameters through the lumen's own centroid per frame, the minimal-lumen-area frame, percent area stenosis), slices in the order
     ``analysis`` uses;
+    ``contours`` (default false): also write ``{save_dir}/contours.json``, the outlines of the same stack as integer polygons along the pixel
+    sides with their holes (``contours.contour_report``; its ``convention`` key states the coordinates), slices in the order ``analysis`` uses;
     ``folds`` (default false), ``tta`` (``none`` | ``flips`` | ``d4``, default ``none``), ``vote`` (``soft`` | ``majority``, default ``soft``): with
     ``folds`` true or a ``tta`` the stack is voted by every ``fold_<k>`` network of a class on every view (``vote.segment_stack_voted``) and
     ``{save_dir}/vote.json`` (``vote.vote_report``) is written, slices in the order ``analysis`` uses; ``dissent_maps`` (default false) adds
@@ -467,6 +478,9 @@ def main(argv=None):
         from .shape import lumen_report
         order = sorted(range(len(paths)), key=lambda i: os.path.basename(paths[i]))
         _save_lumen(lumen_report(stack[torch.tensor(order, device=stack.device)], [names[i] for i in order]), str(cfg['save_dir']))
+    if bool(cfg.get('contours', False)):
+        order = sorted(range(len(paths)), key=lambda i: os.path.basename(paths[i]))
+        _save_contours(stack[torch.tensor(order, device=stack.device)], [names[i] for i in order], str(cfg['save_dir']))
     log.info(f'Overall computation time: {time.time() - start:.1f} s')
     log.info('Complete')
     return 0

@@ -267,6 +267,64 @@ int exercise_components() {
     return 55;
   return 0;
 }
+// The contour entry points (csrc/contours.hip, csrc/contours_api.cpp) against the stubs: the scratch carving with its per-edge arrays, the memset of
+// the counts inside its range and every grid (the scans' tile counts, the jump rounds) from a single pixel to the largest frame an edge id allows
+// and to the largest capacity; then what they must refuse.
+int exercise_contours() {
+  char* base = (char*)(uintptr_t)0x500000000000ull;
+  auto carve = [&](size_t bytes) { char* r = base; base += (bytes + 4095) / 4096 * 4096 + 4096; dry_register_range(r, bytes); return r; };
+  const int shapes[][4] = {{1, 1, 1, 1}, {3, 97, 130, 5}, {186, 704, 704, 4}, {1, 23169, 23169, 1}, {2, 64, 1 << 22, 16}};      // 23170^2 < 2^29
+  const long long caps[] = {1, 4, 100000, (1ll << 31) - 1};
+  for (auto& sh : shapes) {
+    const int N = sh[0], H = sh[1], W = sh[2], C = sh[3];
+    for (long long ecap : caps) {
+      dry_clear_ranges();
+      const size_t need = octseg_contours_scratch_bytes(N * C, H, W, ecap);
+      if (need == 0 || need <= octseg_contours_scratch_bytes(1, H, W, ecap) - (N * C == 1)) return 60;
+      if (ecap > 1 && (need < octseg_contours_scratch_bytes(N * C, H, W, ecap - 1) || (ecap >= 100000 && need <= octseg_contours_scratch_bytes(N * C, H, W, 1))))
+        return 62;                                  // grows with the capacity (in 256-byte steps)
+      float* a = (float*)carve((size_t)N * H * W * C * 4);
+      void* scratch = carve(need);
+      long long* counts = (long long*)carve((size_t)N * C * 2 * 8);
+      int* ncont = (int*)carve((size_t)N * C * 4);
+      int* table = (int*)carve((size_t)OCTSEG_CONTOUR_FIELDS * 4 * 16);
+      int* verts = (int*)carve(2 * 4 * 16);
+      int* overflow = (int*)carve(4);
+      void* st = (void*)(uintptr_t)0x5000;
+      if (octseg_stack_contour_counts(a, N, H, W, C, counts, st) != 0 ||
+          octseg_stack_contours(a, N, H, W, C, scratch, need, ecap, 16, 16, ncont, table, verts, overflow, st) != 0) {
+        fprintf(stderr, "contours: %s\n", octseg_last_error());
+        return 61;
+      }
+      // refused before anything is enqueued
+      const unsigned long long before = dry_launches() + dry_memops();
+      if (octseg_stack_contour_counts(nullptr, N, H, W, C, counts, st) == 0 || octseg_stack_contour_counts(a, N, H, W, C, nullptr, st) == 0 ||
+          octseg_stack_contour_counts(a, N, H, W, C, (long long*)((char*)counts + 4), st) == 0 ||
+          octseg_stack_contour_counts(a, N, H, W, 17, counts, st) == 0 || octseg_stack_contour_counts(a, 0, H, W, C, counts, st) == 0 ||
+          octseg_stack_contours(a, N, H, W, C, scratch, need - 1, ecap, 16, 16, ncont, table, verts, overflow, st) == 0 ||
+          octseg_stack_contours(a, N, H, W, C, nullptr, need, ecap, 16, 16, ncont, table, verts, overflow, st) == 0 ||
+          octseg_stack_contours(a, N, H, W, C, (char*)scratch + 4, need, ecap, 16, 16, ncont, table, verts, overflow, st) == 0 ||
+          octseg_stack_contours(a, N, H, W, 17, scratch, need, ecap, 16, 16, ncont, table, verts, overflow, st) == 0 ||
+          octseg_stack_contours(a, N, 0, W, C, scratch, need, ecap, 16, 16, ncont, table, verts, overflow, st) == 0 ||
+          octseg_stack_contours(a, N, H, W, C, scratch, need, 0, 16, 16, ncont, table, verts, overflow, st) == 0 ||
+          octseg_stack_contours(a, N, H, W, C, scratch, need, 1ll << 31, 16, 16, ncont, table, verts, overflow, st) == 0 ||
+          octseg_stack_contours(a, N, H, W, C, scratch, need, ecap, 0, 16, ncont, table, verts, overflow, st) == 0 ||
+          octseg_stack_contours(a, N, H, W, C, scratch, need, ecap, 16, 1ll << 31, ncont, table, verts, overflow, st) == 0 ||
+          octseg_stack_contours(a, N, H, W, C, scratch, need, ecap, 16, 16, nullptr, table, verts, overflow, st) == 0 ||
+          octseg_stack_contours(a, N, H, W, C, scratch, need, ecap, 16, 16, ncont, nullptr, verts, overflow, st) == 0 ||
+          octseg_stack_contours(a, N, H, W, C, scratch, need, ecap, 16, 16, ncont, table, nullptr, overflow, st) == 0 ||
+          octseg_stack_contours(a, N, H, W, C, scratch, need, ecap, 16, 16, ncont, table, verts, nullptr, st) == 0)
+        return 63;
+      if (dry_launches() + dry_memops() != before) { fprintf(stderr, "a refused contour call enqueued work\n"); return 64; }
+    }
+  }
+  // an edge id must fit 31 bits; H * W below 2^31 - 1; the vertex words of a call below 2^31
+  if (octseg_contours_scratch_bytes(1, 23170, 23170, 8) != 0 || octseg_contours_scratch_bytes(1, 46341, 46341, 8) != 0 ||
+      octseg_contours_scratch_bytes(0, 8, 8, 8) != 0 || octseg_contours_scratch_bytes(1, 8, 0, 8) != 0 || octseg_contours_scratch_bytes(1, 8, 8, 0) != 0 ||
+      octseg_contours_scratch_bytes(1, 8, 8, 1ll << 31) != 0 || octseg_contours_scratch_bytes(1 << 30, 4, 4, 8) != 0)
+    return 65;
+  return 0;
+}
 }  // namespace
 
 int main() {
@@ -364,6 +422,7 @@ int main() {
   if (const int rc = exercise_distance()) { fprintf(stderr, "exercise_distance -> %d\n", rc); return rc; }
   if (const int rc = exercise_lesions()) { fprintf(stderr, "exercise_lesions -> %d\n", rc); return rc; }
   if (const int rc = exercise_components()) { fprintf(stderr, "exercise_components -> %d\n", rc); return rc; }
+  if (const int rc = exercise_contours()) { fprintf(stderr, "exercise_contours -> %d\n", rc); return rc; }
   if (dry_errors() != 0) { fprintf(stderr, "%llu launch / memory-range violations\n", dry_errors()); return 8; }
   printf("plan_dryrun: %d plans built, %d of them run through forward / backward / optimizer with recording HIP stubs (%llu launches, %llu memory "
          "operations checked) under ASan + UBSan, checksum %llu, 0 errors, launch fingerprint %016llx\n", plans, executed, dry_launches(), dry_memops(), checksum,
