@@ -59,6 +59,9 @@
  *   octseg_volume_components / octseg_volume_cleanup / octseg_lesions_scratch_bytes
  *                                      (no reference counterpart) the connected components of a mask stack across its slices: labels, the 32
  *                                      largest lesions per class with their extents, the per-slice area profile, the flicker filter
+ *   octseg_volume_match / octseg_match_scratch_bytes
+ *                                      (no reference counterpart) predicted against annotated lesions: both stacks' ranked lesions, the 33 x 33
+ *                                      table of shared voxels by lesion rank per class, per-slice |P & T|, |P|, |T|
  *   octseg_volume_normalize            cv2.normalize(slice, None, 0, 255, NORM_MINMAX, CV_8U) + cvtColor(BGR2RGB) of every slice of a DICOM's
  *                                      pixel_array (src/data/convert_dicoms.py:71-81, src/app/tools/analysis.py:167-177)
  *   octseg_resize_pil_u8               data_processing's Image.open(p).resize(output_size), Pillow's default BICUBIC (src/data/utils.py:187)
@@ -546,6 +549,35 @@ int octseg_volume_components(const float* stack, int N, int H, int W, int channe
                              int* nles, int* top, int* profile, void* stream);
 int octseg_volume_cleanup(const float* stack, int N, int H, int W, int channels, int across, int keep, int min_voxels, int min_slices, void* scratch,
                           size_t scratch_bytes, float* out, int* nles, int* top, void* stream);
+
+/* Predicted against annotated lesions (no reference counterpart: the reference scores pixel overlap only; DESIGN.md section 5o, pinned to
+ * tests/match_ref.py, which is proved against sklearn's contingency_matrix).  pred, truth: device f32 [N][H][W][channels] with the same extents, any
+ * value != 0 is set; they may be the same buffer and neither is modified.  Channels are independent.  For a channel and a SIDE (0 = pred, 1 = truth)
+ * the lesions, their labels and their ranked list are exactly those of octseg_volume_components above with the same `across`: the 32 largest by
+ * voxels descending, then first voxel ascending.  The RANK of a set voxel is 0..31 if its lesion is ranked and 32 ("rest") if its lesion is beyond
+ * the 32 listed; a clear voxel has no rank.
+ *   nles    int32 [channels][2]: the number of lesions per side;
+ *   top     int32 [channels][2][32][8] (optional): the rows of octseg_volume_components' top for each side, bounding boxes included;
+ *   overlap int32 [channels][33][33]: overlap[i][j] = the voxels whose pred rank is i and whose truth rank is j.  The table sums to |P & T| of the
+ *           channel; row i < 32 sums to at most top[c][0][i][0], the remainder of the lesion lies over truth background (columns alike);
+ *   frames  int32 [channels][N][3] (optional): |P & T|, |P|, |T| set pixels of slice n.
+ * Everything is integer and a function of the two stacks alone: two runs are bit-equal, results EQUAL the restatement's, no tolerance.  overlap and
+ * frames are cleared inside the call.
+ * scratch: device, 8-byte aligned, scratch_bytes >= octseg_match_scratch_bytes(channels, N, H, W) (0 for extents the call refuses), which is, with
+ * V = channels * N * H * W, al(v) = v rounded up to 256 and W64 = ceil(W / 64):
+ *   4 * al(4 * V)                                             parent of either side; voxel counts and last slices, used by one side after the other
+ *   + al(4 * channels * N * ceil(H / 2) * ceil(W / 2))        the lesion list, likewise shared
+ *   + 2 * al(4 * channels)                                    the lesion counter and the threshold
+ *   + 2 * al(4 * channels * 32)                               the ranked roots of either side
+ *   + al(4 * channels * 2) + al(4 * channels * 2 * 32 * 8)    nles and top side by side, before they are interleaved
+ *   + 2 * al(8 * channels * N * H * W64)                      the bit planes of either side
+ * (about 17.3 bytes per voxel and channel, against 2 x 13.3 for two octseg_volume_components calls' worth).
+ * Enqueue only, nothing is allocated.  Null pred / truth / scratch / nles / overlap, scratch too small or not 8-byte aligned, unknown across:
+ * OCTSEG_BAD_ARG; N, H, W <= 0, channels outside 1..16, N * H * W >= 2^31 - 1: OCTSEG_BAD_SHAPE.  Every refusal happens before any HIP call:
+ * nothing is launched, no output is touched, and octseg_last_error names the argument. */
+size_t octseg_match_scratch_bytes(int channels, int N, int H, int W);
+int octseg_volume_match(const float* pred, const float* truth, int N, int H, int W, int channels, int across, void* scratch, size_t scratch_bytes,
+                        int* nles, int* top, int* overlap, int* frames, void* stream);
 
 /* Boundary distances (no reference counterpart: the reference scores overlap only; what is restated here are the definitions of DESIGN.md
  * section 5i, pinned to scipy.ndimage by tests/distance_ref.py).  stack / src / dst: device f32 [N][H][W][channels], any value != 0 is set; a plane

@@ -165,6 +165,10 @@ SYMBOLS = {
     'octseg_lesions_scratch_bytes': (C.c_size_t, [C.c_int] * 4),
     'octseg_volume_components': (C.c_int, [_P] + [C.c_int] * 5 + [_P, C.c_size_t, _P, _P, _P, _P, _P]),
     'octseg_volume_cleanup': (C.c_int, [_P] + [C.c_int] * 8 + [_P, C.c_size_t, _P, _P, _P, _P]),
+    # two float32 mask stacks -> both sides' ranked lesions, the 33 x 33 table of shared voxels by lesion rank, per-slice |P & T|, |P|, |T|
+    # (csrc/match.hip)
+    'octseg_match_scratch_bytes': (C.c_size_t, [C.c_int] * 4),
+    'octseg_volume_match': (C.c_int, [_P, _P] + [C.c_int] * 5 + [_P, C.c_size_t, _P, _P, _P, _P, _P]),
     # float32 mask stacks -> boundary planes, exact squared distance maps, per (slice, channel pair) counts, keyed distance lists and the
     # minimum with its location (csrc/distance.hip)
     'octseg_distance_scratch_bytes': (C.c_size_t, [C.c_int] * 6),

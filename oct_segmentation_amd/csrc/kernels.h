@@ -417,6 +417,13 @@ hipError_t launch_volume_components(const float* stack, int N, int H, int W, int
 hipError_t launch_volume_cleanup(const float* stack, int N, int H, int W, int C, int full, int keep, int min_voxels, int min_slices, void* scratch,
                                  float* out, int* nles, int* top, hipStream_t st);
 
+// predicted against annotated lesions (match.hip): both stacks labelled and ranked as above, then per channel the 33 x 33 table of the voxels both
+// set by the rank of their lesion on either side (32 = beyond the 32 listed) and |P & T|, |P|, |T| per slice.  scratch: match_scratch_bytes(C, N,
+// H, W) device bytes; nles int32 [C][2], overlap int32 [C][33][33]; top int32 [C][2][32][8] and frames int32 [C][N][3] are optional
+size_t match_scratch_bytes(size_t channels, int N, int H, int W);
+hipError_t launch_volume_match(const float* pred, const float* truth, int N, int H, int W, int C, int full, void* scratch, int* nles, int* top,
+                               int* overlap, int* frames, hipStream_t st);
+
 // boundary distances (distance.hip): the boundary of every plane, the exact squared Euclidean distance map (column pass + row minimum in LDS), and
 // per (slice, pair of channels) the counts, the keyed list of d2 at the query pixels, and their minimum with its location.  scratch:
 // distance_scratch_bytes(N, H, W, Ca, Cb, pairs) device bytes (one-stack calls: Cb = 0, pairs = 0).  part / to: 0 set, 1 clear, 2 boundary

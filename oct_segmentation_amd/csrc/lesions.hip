@@ -33,13 +33,13 @@
 
 #include "bitplanes.h"
 #include "kernels.h"
+#include "lesions_internal.h"
 
 namespace octseg {
 
 namespace {
 
 constexpr int SEL_NT = 256;               // workgroup of vol_select_kernel (a power of two)
-constexpr int TOPL = 32, LCOL = 8;        // the table: voxels, first_voxel, z0, z1, y0, y1, x0, x1
 
 // one unite per maximal run of m: voxel a0 + s with voxel a0 + s + off, s the run's first bit
 __device__ __forceinline__ void unite_runs(int* par, u64 m, int a0, int off) {
@@ -81,9 +81,7 @@ __global__ __launch_bounds__(NT) void vol_across_kernel(const u64* __restrict__ 
 // ---- per-run kernels, a thread per word.  Runs that share a destination are summed inside the wave first (a big lesion's runs all add to one
 // root: one atomic per run serialises on that address), then ONE lane issues the atomics.  All 64 lanes of a wave take every step below together:
 // the grid-stride loop runs on the block's base index, and the run loop goes on while any lane still has a run.
-__device__ __forceinline__ int wave_sum(int v) { for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o); return v; }
-__device__ __forceinline__ int wave_min(int v) { for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o)); return v; }
-__device__ __forceinline__ int wave_max(int v) { for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o)); return v; }
+// (wave_sum / wave_min / wave_max: lesions_internal.h)
 
 __global__ __launch_bounds__(NT) void vol_count_kernel(const u64* __restrict__ bits, int C, BitGeo g, const int* __restrict__ parent, int* __restrict__ vox,
                                                        int* __restrict__ zmax, int* __restrict__ list, int* __restrict__ nroots, int cap) {
@@ -274,17 +272,10 @@ __global__ __launch_bounds__(NT) void vol_extent_kernel(const u64* __restrict__ 
 
 namespace {
 
-struct VScratch {
-  int *parent, *vox, *zmax, *list, *nroots, *thr, *rank;
-  u64 *a, *b;
-  int cap;
-  size_t bytes;
-};
-
 VScratch carve(void* base, size_t C, int N, int H, int W) {
   VScratch s;
   const size_t NHW = (size_t)N * H * W, W64 = ((size_t)W + 63) / 64;
-  s.cap = (int)((size_t)N * (((size_t)H + 1) / 2) * (((size_t)W + 1) / 2));
+  s.cap = lesion_capacity(N, H, W);
   Carver cv(base);
   s.parent = cv.take<int>(C * NHW);
   s.vox = cv.take<int>(C * NHW);
@@ -299,7 +290,9 @@ VScratch carve(void* base, size_t C, int N, int H, int W) {
   return s;
 }
 
-// pack and label; with `rank` also count and select: the threshold, the count and the ranking
+}  // namespace
+
+// pack and label; with `rank` also count and select: the threshold, the count and the ranking (shared with match.hip: lesions_internal.h)
 hipError_t label_and_rank(const float* stack, const BitGeo& g, int C, int full, bool rank, int keep, int min_voxels, int min_slices, const VScratch& s,
                           int* nles, int* top, hipStream_t st) {
   const unsigned gt = item_grid((size_t)C * g.words());
@@ -317,7 +310,7 @@ hipError_t label_and_rank(const float* stack, const BitGeo& g, int C, int full, 
   return hipSuccess;
 }
 
-hipError_t extents(const BitGeo& g, int C, const VScratch& s, int* top, int* profile, hipStream_t st) {
+hipError_t volume_extents(const BitGeo& g, int C, const VScratch& s, int* top, int* profile, hipStream_t st) {
   if (profile) {
     hipError_t e = hipMemsetAsync(profile, 0, (size_t)C * TOPL * g.D * sizeof(int), st);
     if (e != hipSuccess) return e;
@@ -326,8 +319,6 @@ hipError_t extents(const BitGeo& g, int C, const VScratch& s, int* top, int* pro
   hipLaunchKernelGGL(vol_extent_kernel, dim3(gx, C), dim3(NT), 0, st, s.a, g, s.parent, s.rank, top, profile);
   return hipSuccess;
 }
-
-}  // namespace
 
 size_t lesions_scratch_bytes(size_t channels, int N, int H, int W) { return carve(nullptr, channels, N, H, W).bytes; }
 
@@ -339,7 +330,7 @@ hipError_t launch_volume_components(const float* stack, int N, int H, int W, int
   if (e != hipSuccess) return e;
   if (labels) launch_ccl_labels(s.a, C, g, s.parent, labels, st);
   if (top || profile) {
-    e = extents(g, C, s, top, profile, st);
+    e = volume_extents(g, C, s, top, profile, st);
     if (e != hipSuccess) return e;
   }
   return hipGetLastError();
@@ -352,7 +343,7 @@ hipError_t launch_volume_cleanup(const float* stack, int N, int H, int W, int C,
   hipError_t e = label_and_rank(stack, g, C, full, true, keep, min_voxels, min_slices, s, nles, top, st);
   if (e != hipSuccess) return e;
   if (top) {
-    e = extents(g, C, s, top, nullptr, st);
+    e = volume_extents(g, C, s, top, nullptr, st);
     if (e != hipSuccess) return e;
   }
   launch_ccl_keep(s.a, C, g, s.parent, s.vox, s.zmax, s.thr, min_slices, s.b, st);

@@ -6,7 +6,7 @@
 // encoder pair at the smallest legal frame, the benchmark frame and a non-square one, in all three dtypes, with no kernel launched
 // (no GPU needed).  A subset of the plans is then driven through octseg_net_forward / _backward / _backward_sliced / octseg_optim_step and
 // the graph-captured eval forward, and the class-activation-map path (frozen forward, seeded backward, map launches) against tools/hip_host_stubs.cpp, a recording stand-in for the HIP runtime that checks every launch
-// geometry and every memset / copy range; the boundary-distance entry points (csrc/distance.hip), the 3-D lesion entry points (csrc/lesions.hip) and the
+// geometry and every memset / copy range; the boundary-distance entry points (csrc/distance.hip), the 3-D lesion entry points (csrc/lesions.hip), the lesion-matching entry points (csrc/match.hip) and the
 // mask clean-up entry points (csrc/components.hip) are driven the same way, from a 1 x 1 frame to the largest one each takes.  Exit code 0 = the sanitizers and the stubs saw nothing.
 #include <cstdio>
 #include <cstring>
@@ -208,6 +208,58 @@ int exercise_lesions() {
   }
   if (octseg_lesions_scratch_bytes(1, 2048, 1024, 1024) != 0 || octseg_lesions_scratch_bytes(17, 2, 8, 8) != 0 || octseg_lesions_scratch_bytes(1, 0, 8, 8) != 0)
     return 45;
+  return 0;
+}
+
+// The lesion-matching entry points (csrc/match.hip, csrc/match_api.cpp) against the stubs: the scratch carving of two labellings that share their
+// counters, the memsets (overlap, frames, the lesion counter of either side) inside their ranges and every grid, from a single voxel to a volume
+// just under 2^31 - 1 voxels, with and without the optional outputs and with one buffer on both sides; then what the call must refuse.
+int exercise_match() {
+  char* base = (char*)(uintptr_t)0x500000000000ull;
+  auto carve = [&](size_t bytes) { char* r = base; base += (bytes + 4095) / 4096 * 4096 + 4096; dry_register_range(r, bytes); return r; };
+  const int shapes[][4] = {{1, 1, 1, 1}, {5, 97, 130, 5}, {186, 704, 704, 4}, {2047, 1024, 1024, 16}};
+  for (auto& sh : shapes) {
+    dry_clear_ranges();
+    const int N = sh[0], H = sh[1], W = sh[2], C = sh[3];
+    const size_t need = octseg_match_scratch_bytes(C, N, H, W);
+    if (need == 0 || need <= octseg_match_scratch_bytes(1, N, H, W) - (C == 1) || need <= octseg_lesions_scratch_bytes(C, N, H, W)) return 70;
+    const size_t elems = (size_t)N * H * W * C;
+    float* a = (float*)carve(elems * 4);
+    float* b = (float*)carve(elems * 4);
+    void* scratch = carve(need);
+    int* nles = (int*)carve((size_t)C * 2 * 4);
+    int* top = (int*)carve((size_t)C * 2 * 32 * 8 * 4);
+    int* overlap = (int*)carve((size_t)C * 33 * 33 * 4);
+    int* frames = (int*)carve((size_t)C * N * 3 * 4);
+    void* st = (void*)(uintptr_t)0x5000;
+    for (int across = 0; across < 2; ++across) {
+      if (octseg_volume_match(a, b, N, H, W, C, across, scratch, need, nles, top, overlap, frames, st) != 0) {
+        fprintf(stderr, "volume_match: %s\n", octseg_last_error());
+        return 71;
+      }
+      if (octseg_volume_match(a, a, N, H, W, C, across, scratch, need, nles, nullptr, overlap, nullptr, st) != 0) return 71;
+      if (octseg_volume_match(a, b, N, H, W, C, across, scratch, need, nles, top, overlap, nullptr, st) != 0) return 71;
+      if (octseg_volume_match(a, b, N, H, W, C, across, scratch, need, nles, nullptr, overlap, frames, st) != 0) return 71;
+    }
+    // refused before anything is enqueued
+    const unsigned long long before = dry_launches() + dry_memops();
+    if (octseg_volume_match(nullptr, b, N, H, W, C, 0, scratch, need, nles, top, overlap, frames, st) == 0 ||
+        octseg_volume_match(a, nullptr, N, H, W, C, 0, scratch, need, nles, top, overlap, frames, st) == 0 ||
+        octseg_volume_match(a, b, N, H, W, C, 0, nullptr, need, nles, top, overlap, frames, st) == 0 ||
+        octseg_volume_match(a, b, N, H, W, C, 0, scratch, need, nullptr, top, overlap, frames, st) == 0 ||
+        octseg_volume_match(a, b, N, H, W, C, 0, scratch, need, nles, top, nullptr, frames, st) == 0 ||
+        octseg_volume_match(a, b, N, H, W, C, 0, scratch, need - 1, nles, top, overlap, frames, st) == 0 ||
+        octseg_volume_match(a, b, N, H, W, C, 2, scratch, need, nles, top, overlap, frames, st) == 0 ||
+        octseg_volume_match(a, b, N, H, W, 17, 0, scratch, need, nles, top, overlap, frames, st) == 0 ||
+        octseg_volume_match(a, b, N, H, W, 0, 0, scratch, need, nles, top, overlap, frames, st) == 0 ||
+        octseg_volume_match(a, b, 0, H, W, C, 0, scratch, need, nles, top, overlap, frames, st) == 0 ||
+        octseg_volume_match(a, b, N, H, W, C, 0, (char*)scratch + 4, need, nles, top, overlap, frames, st) == 0)
+      return 72;
+    if (dry_launches() + dry_memops() != before) { fprintf(stderr, "a refused match call enqueued work\n"); return 73; }
+  }
+  if (octseg_volume_match((float*)8, (float*)8, 2048, 1024, 1024, 1, 0, (void*)8, (size_t)1 << 60, (int*)8, nullptr, (int*)8, nullptr, nullptr) == 0) return 74;
+  if (octseg_match_scratch_bytes(1, 2048, 1024, 1024) != 0 || octseg_match_scratch_bytes(17, 2, 8, 8) != 0 || octseg_match_scratch_bytes(1, 0, 8, 8) != 0)
+    return 75;
   return 0;
 }
 
@@ -421,6 +473,7 @@ int main() {
   for (int dt = 0; dt < 3; ++dt) checksum += octseg_conv2d_scratch_bytes(dt, 2, 64, 64, 24, 40, 3, 3) + octseg_conv2d_scratch_bytes(dt, 1, 8, 8, 2048, 512, 1, 1);
   if (const int rc = exercise_distance()) { fprintf(stderr, "exercise_distance -> %d\n", rc); return rc; }
   if (const int rc = exercise_lesions()) { fprintf(stderr, "exercise_lesions -> %d\n", rc); return rc; }
+  if (const int rc = exercise_match()) { fprintf(stderr, "exercise_match -> %d\n", rc); return rc; }
   if (const int rc = exercise_components()) { fprintf(stderr, "exercise_components -> %d\n", rc); return rc; }
   if (const int rc = exercise_contours()) { fprintf(stderr, "exercise_contours -> %d\n", rc); return rc; }
   if (dry_errors() != 0) { fprintf(stderr, "%llu launch / memory-range violations\n", dry_errors()); return 8; }
