@@ -56,6 +56,10 @@
  *   octseg_stack_boundary / octseg_stack_distance / octseg_pair_distance_counts / _keys / _min / octseg_distance_scratch_bytes
  *                                      (no reference counterpart) exact squared Euclidean distance maps of the mask planes, the directed
  *                                      boundary-distance lists behind HD / HD95 / ASSD, the smallest distance between two classes
+ *   octseg_volume_boundary / octseg_volume_distance / octseg_volume_pair_distance_counts / _keys / _min / octseg_volume_distance_scratch_bytes
+ *                                      (no reference counterpart) the same over the volume the slices form, slice_step pixels apart: the
+ *                                      6-neighbour boundary, exact 3-D squared distance maps in bands of rows, the volumetric HD / HD95 / ASSD
+ *                                      lists per pair of channels, the smallest distance across slices with its voxel
  *   octseg_volume_components / octseg_volume_cleanup / octseg_lesions_scratch_bytes
  *                                      (no reference counterpart) the connected components of a mask stack across its slices: labels, the 32
  *                                      largest lesions per class with their extents, the per-slice area profile, the flicker filter
@@ -618,6 +622,54 @@ int octseg_pair_distance_keys(const float* src, const float* dst, int N, int H, 
                               long long* keys, long long capacity, int* overflow, void* stream);
 int octseg_pair_distance_min(const float* src, const float* dst, int N, int H, int W, int channels_a, int channels_b, const int* pairs, int npairs,
                              int src_part, int dst_part, void* scratch, size_t scratch_bytes, unsigned long long* out, void* stream);
+
+/* Surface distances of the VOLUME (no reference counterpart; DESIGN.md section 5p, pinned to scipy.ndimage by tests/distance3d_ref.py).  The stack
+ * f32 [N][H][W][channels], any value != 0 set, is read per channel as a volume of N slices; voxel (z, y, x) is pixel (y, x) of slice z.
+ * slice_step: an integer s >= 1, the distance between neighbouring slices in pixels.  The squared distance between two voxels is
+ *   (s dz)^2 + dy^2 + dx^2, voxel centre to voxel centre, in int32; only integers are accepted, rational spacing is out of scope.
+ * The 3-D BOUNDARY is b = m & ~erode(m) with the 6-neighbour cross, everything outside the volume clear
+ *   (scipy: m & ~binary_erosion(m, generate_binary_structure(3, 1), border_value=0)): every set voxel of the first and of the last slice is boundary,
+ *   and with N <= 2 every set voxel is.  There is no "open ends" variant.
+ * A PART is 0 the set voxels, 1 the clear voxels inside the volume, or 2 the 3-D boundary.  The TARGET of a distance is the part taken over the
+ * whole volume of one channel: d2(z, y, x) = min over the target's voxels (scipy: rint(distance_transform_edt(~T, sampling=(s, 1, 1))^2)), 0 on the
+ * target, OCTSEG_DIST_NONE everywhere when the part is empty in the whole volume -- that is not decided per slice.  Integer arithmetic only: results
+ * EQUAL the restatement's, no tolerance.
+ * scratch: device, 8-byte aligned.  octseg_volume_distance_scratch_bytes(N, H, W, channels_a, channels_b, pairs, rows) = the bytes a call needs that
+ * maps the volume in BANDS of `rows` rows of all slices (1 <= rows <= H; rows = 0: octseg_volume_boundary and the counts, which take no distance);
+ * one-stack calls: channels_b = 0, pairs = 0; 0 is returned for arguments the calls refuse.  The bit planes of the whole volume (1/8 byte per voxel
+ * and plane, four sets at most) plus 6 bytes per voxel of the band and target channel.  octseg_volume_distance and the keys / min calls take the most
+ * rows that fit scratch_bytes and work band after band; the result does not depend on the banding.  A scratch below the one-row need is refused with
+ * the bytes needed in octseg_last_error.
+ *
+ * octseg_volume_boundary: out f32 [N][H][W][channels] (0.0 / 1.0, must not alias stack) = the 3-D boundary.
+ * octseg_volume_distance: d2 int32 [N][channels][H][W] = the squared distance of every voxel to part `to` of its own channel's volume.
+ * The pair calls take pairs int32 [npairs][2] = (channel of src, channel of dst) as octseg_pair_distance_* do, clamped on the device; a SEGMENT is a
+ * pair p, not a (slice, pair): the QUERY voxels are part src_part of src's channel over all slices, the TARGET part dst_part of dst's channel.
+ * octseg_volume_pair_distance_counts: counts int64 [npairs][2] = query voxels, target voxels; overlap (may be NULL) int64 [npairs][3] =
+ *   |a & b|, |a|, |b| of the two channels' SET voxels whatever the parts.
+ * octseg_volume_pair_distance_keys: one int64 key = (first_segment + p) << 32 | d2 per query voxel at keys[offsets[p] + slot], offsets device int64
+ *   [npairs], slots in no fixed order: sort the keys.  A position outside 0 .. capacity - 1 is NOT stored and sets *overflow (device int32, cleared
+ *   by the caller) to 1: never a store past the buffer.
+ * octseg_volume_pair_distance_min: out uint64 [npairs] = the minimum over the pair's query voxels of d2 << 32 | (z * H * W + y * W + x): the
+ *   smallest squared distance and, among the voxels that attain it, the first in raster order; all ones without a query voxel.
+ * Enqueue only, nothing is allocated.  Null pointer (overlap excepted), scratch too small or misaligned, a part outside 0..2, capacity <= 0, out ==
+ * stack, slice_step < 1 or slice_step * (N - 1) > 32767 (so that d2 < 2^30 + 2^25 stays below OCTSEG_DIST_NONE), N * H * W > 2^32 (the packed
+ * minimum's voxel index): OCTSEG_BAD_ARG; N, H, W <= 0, H or W above 4096, channels outside 1..16, npairs <= 0, N * npairs or a segment number
+ * reaching 2^31: OCTSEG_BAD_SHAPE.  Nothing is launched then. */
+size_t octseg_volume_distance_scratch_bytes(int N, int H, int W, int channels_a, int channels_b, int pairs, int rows);
+int octseg_volume_boundary(const float* stack, int N, int H, int W, int channels, void* scratch, size_t scratch_bytes, float* out, void* stream);
+int octseg_volume_distance(const float* stack, int N, int H, int W, int channels, int to, int slice_step, void* scratch, size_t scratch_bytes, int* d2,
+                           void* stream);
+int octseg_volume_pair_distance_counts(const float* src, const float* dst, int N, int H, int W, int channels_a, int channels_b, const int* pairs,
+                                       int npairs, int src_part, int dst_part, void* scratch, size_t scratch_bytes, long long* counts,
+                                       long long* overlap /* may be NULL */, void* stream);
+int octseg_volume_pair_distance_keys(const float* src, const float* dst, int N, int H, int W, int channels_a, int channels_b, const int* pairs,
+                                     int npairs, int src_part, int dst_part, int slice_step, void* scratch, size_t scratch_bytes,
+                                     long long first_segment, const long long* offsets, long long* keys, long long capacity, int* overflow,
+                                     void* stream);
+int octseg_volume_pair_distance_min(const float* src, const float* dst, int N, int H, int W, int channels_a, int channels_b, const int* pairs, int npairs,
+                                    int src_part, int dst_part, int slice_step, void* scratch, size_t scratch_bytes, unsigned long long* out,
+                                    void* stream);
 
 /* The arithmetic between a DICOM's pixel_array and the frames the pipeline takes (reference src/data/convert_dicoms.py:71-81, repeated in
  * src/app/tools/analysis.py:167-177): per slice cv2.normalize(img, None, alpha=0, beta=255, norm_type=NORM_MINMAX, dtype=CV_8U), then

@@ -178,6 +178,15 @@ SYMBOLS = {
     'octseg_pair_distance_keys': (C.c_int, [_P, _P] + [C.c_int] * 5 + [_P] + [C.c_int] * 3 + [_P, C.c_size_t, C.c_longlong, _P, _P, C.c_longlong,
                                             _P, _P]),
     'octseg_pair_distance_min': (C.c_int, [_P, _P] + [C.c_int] * 5 + [_P] + [C.c_int] * 3 + [_P, C.c_size_t, _P, _P]),
+    # the same over the volume a channel's slices form, slice_step pixels apart: 6-neighbour boundary, 3-D distance map in bands of rows, per-pair
+    # int64 counts, keyed lists and the minimum with its voxel (csrc/distance.hip)
+    'octseg_volume_distance_scratch_bytes': (C.c_size_t, [C.c_int] * 7),
+    'octseg_volume_boundary': (C.c_int, [_P] + [C.c_int] * 4 + [_P, C.c_size_t, _P, _P]),
+    'octseg_volume_distance': (C.c_int, [_P] + [C.c_int] * 6 + [_P, C.c_size_t, _P, _P]),
+    'octseg_volume_pair_distance_counts': (C.c_int, [_P, _P] + [C.c_int] * 5 + [_P] + [C.c_int] * 3 + [_P, C.c_size_t, _P, _P, _P]),
+    'octseg_volume_pair_distance_keys': (C.c_int, [_P, _P] + [C.c_int] * 5 + [_P] + [C.c_int] * 4 + [_P, C.c_size_t, C.c_longlong, _P, _P,
+                                                   C.c_longlong, _P, _P]),
+    'octseg_volume_pair_distance_min': (C.c_int, [_P, _P] + [C.c_int] * 5 + [_P] + [C.c_int] * 4 + [_P, C.c_size_t, _P, _P]),
     # raw volume [S,H,W,C] uint8 | uint16 -> per-slice min / max + uint8 RGB frames; Pillow's 8-bit bicubic resize from tables (csrc/volume.hip)
     'octseg_volume_normalize': (C.c_int, [_P] + [C.c_int] * 6 + [_P, _P, _P]),
     'octseg_resize_pil_u8': (C.c_int, [_P] + [C.c_int] * 4 + [_P, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, C.c_int, _P]),

@@ -1,7 +1,8 @@
 // distance.hip -- exact Euclidean distance maps of the mask stacks the pipeline carries, and what is read off them: the boundary of every plane,
 // the squared distance of every pixel to the nearest target pixel, the directed boundary-to-boundary distance lists behind the Hausdorff
 // family (HD, HD95, ASSD), the smallest distance between two classes with the pixel that attains it, and the overlap counts of the same
-// planes.  No reference counterpart: the reference reports overlap scores only (DESIGN.md section 5i states the definitions).
+// planes.  No reference counterpart: the reference reports overlap scores only (DESIGN.md section 5i states the definitions).  The second half of the
+// file does the same over the volume a channel's planes form (section 5p; its own comment below).
 //
 // A plane is one (slice, channel) pair of the float32 stack [N][H][W][C], any value != 0 set.  Planes live as the bit planes of bitplanes.h, every
 // plane on its own (its geometry with D = 1); pack and unpack are the shared kernels of bitplanes.hip.  Everything is integer arithmetic on
@@ -322,6 +323,299 @@ hipError_t launch_pair_distance_query(const float* src, const float* dst, int N,
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(dist_query_kernel, dim3(block_grid((size_t)N * P * g.H)), dim3(NT), 0, st, s.qa, s.g, s.any, N, g, Ca, Cb, pairs, P, seg0, offsets,
                      s.cursor, keys, capacity, overflow, (u64*)minout);
+  return hipGetLastError();
+}
+
+// ==== the same over the VOLUME a channel's N planes form.  Voxel (z, y, x) of a channel is pixel (y, x) of its plane in slice z;
+// neighbouring slices lie s = slice_step pixels apart, an integer, so d2 = (s dz)^2 + dy^2 + dx^2 stays exact in int32: s (N - 1) <= 32767 keeps it
+// below 2^30 + 2^25.  The squared distance is separable: d2_3(z, y, x) = min over z' of d2_2(z', y, x) + (s (z - z'))^2, a third pass along the slice
+// axis over the per-slice map the column pass and row_min give.  That map is never held whole: the slice-axis pass is independent per (y, x), so a
+// BAND of rows y0 .. y0 + rows - 1 of ALL slices is mapped, passed along z and consumed, band after band, each band three launches.
+//
+//   part      as above, with the boundary's erosion also ANDed with the same word of slices n - 1 and n + 1 (the 6-neighbour cross; slices outside
+//             0 .. N - 1 read as zero, so every set voxel of the first and last slice is boundary).  Two flags: any[plane] as above (a slice whose
+//             2-D target is empty is skipped by the column pass and mapped to DIST_NONE) and anyvol[channel], the target of a DISTANCE: where it is 0
+//             the result is DIST_NONE for the whole volume and the search along z is not run.
+//   column    as above, a thread per (plane, column), but only the band's rows of g are stored: the scans still run the whole column, reading bits
+//   map       dist_map_kernel over the band's rows: int32 [N * C planes][rows][W]; DIST_NONE on an empty plane
+//   slice min a thread per voxel of the band, lanes on consecutive x, so every load along z is coalesced: best = the voxel's own slice, then k = 1,
+//             2, ... testing z - k and z + k until (s k)^2 >= best or both have left the volume.  DIST_NONE entries are infinite: never added to.
+//             Bounded by N, best only falls.
+//   query     the slice minimum at the query voxels of the source part only; a SEGMENT is a pair.  keys: the wave's query lanes take their slots
+//             from one 64-bit atomic of the wave's first query lane; min: a 64-bit atomicMin of d2 << 32 | (z H W + y W + x), N H W <= 2^32.
+//   count     dist_count_kernel per (slice, pair) into scratch, then a thread per (pair, counter) sums the slices into int64.
+namespace {
+
+__device__ __forceinline__ int slice_min(const int* __restrict__ col, size_t stride, int N, int z, int s) {
+  int best = col[(size_t)z * stride];
+  for (int k = 1; k < N; ++k) {
+    const int sk = s * k, k2 = sk * sk;                            // s k <= 32767
+    if (k2 >= best) break;
+    const bool l = z - k >= 0, r = z + k < N;
+    if (!l && !r) break;
+    if (l) { const int a = col[(size_t)(z - k) * stride]; if (a != DIST_NONE) best = min(best, k2 + a); }
+    if (r) { const int a = col[(size_t)(z + k) * stride]; if (a != DIST_NONE) best = min(best, k2 + a); }
+  }
+  return best;
+}
+
+}  // namespace
+
+// ---- the part of every plane, planes [N][C]; any [N * C] and anyvol [C] (either may be null) cleared by the caller
+__global__ __launch_bounds__(NT) void dist_part3_kernel(const u64* __restrict__ src, u64* __restrict__ dst, int N, int C, BitGeo g, int part,
+                                                        int* __restrict__ any, int* __restrict__ anyvol) {
+  const size_t words = (size_t)g.H * g.W64, total = (size_t)N * C * words;
+  for (size_t it = (size_t)blockIdx.x * NT + threadIdx.x; it < total; it += (size_t)gridDim.x * NT) {
+    const int j = (int)(it % g.W64), y = (int)((it / g.W64) % g.H);
+    const size_t pl = it / words;
+    const int n = (int)(pl / C);
+    const u64* plane = src + pl * words;
+    const u64 w = src[it];
+    u64 o;
+    if (part == 0) {
+      o = w;
+    } else if (part == 1) {
+      o = ~w & inmask(j, g.W);
+    } else {
+      o = 0ull;
+      if (w) {
+        const u64 prev = rdw(plane, y, j - 1, g), next = rdw(plane, y, j + 1, g);
+        const u64 before = n > 0 ? src[it - (size_t)C * words] : 0ull, after = n + 1 < N ? src[it + (size_t)C * words] : 0ull;
+        const u64 ero = w & rdw(plane, y - 1, j, g) & rdw(plane, y + 1, j, g) & ((w << 1) | (prev >> 63)) & ((w >> 1) | (next << 63)) & before & after;
+        o = w & ~ero;
+      }
+    }
+    dst[it] = o;
+    if (o) {
+      if (any) any[pl] = 1;
+      if (anyvol) anyvol[pl % C] = 1;
+    }
+  }
+}
+
+// ---- column pass of a band: a thread per (plane, column) scans the whole column from the bits and stores rows y0 .. y0 + rb - 1, gband [P][rb][W]
+__global__ __launch_bounds__(NT) void dist_column_band_kernel(const u64* __restrict__ bits, int P, BitGeo g, const int* __restrict__ any, int y0, int rb,
+                                                              u16* __restrict__ gband) {
+  const size_t total = (size_t)P * g.W;
+  const int y1 = min(y0 + rb, g.H);
+  for (size_t it = (size_t)blockIdx.x * NT + threadIdx.x; it < total; it += (size_t)gridDim.x * NT) {
+    const int x = (int)(it % g.W);
+    const size_t pl = it / g.W;
+    if (!any[pl]) continue;
+    const u64* col = bits + pl * g.H * g.W64 + (x >> 6);
+    u16* gc = gband + pl * rb * g.W + x;
+    const int sh = x & 63;
+    int d = G_NONE;
+#pragma unroll 4
+    for (int y = 0; y < y1; ++y) {
+      if ((col[(size_t)y * g.W64] >> sh) & 1ull) d = 0; else if (d != G_NONE) ++d;
+      if (y >= y0) gc[(size_t)(y - y0) * g.W] = (u16)d;
+    }
+    d = G_NONE;
+#pragma unroll 4
+    for (int y = g.H - 1; y >= y0; --y) {
+      if ((col[(size_t)y * g.W64] >> sh) & 1ull) d = 0; else if (d != G_NONE) ++d;
+      if (y < y1 && d < (int)gc[(size_t)(y - y0) * g.W]) gc[(size_t)(y - y0) * g.W] = (u16)d;
+    }
+  }
+}
+
+// ---- slice-axis pass of a band into the full map: a thread per (slice, channel, band row, x).  d2band [N * C][rb][W], out [N][C][H][W]
+__global__ __launch_bounds__(NT) void dist_slice_map_kernel(const int* __restrict__ d2band, const int* __restrict__ anyvol, int N, int C, int H, int W,
+                                                            int y0, int rb, int s, int* __restrict__ out) {
+  const size_t total = (size_t)N * C * rb * W, stride = (size_t)C * rb * W;
+  for (size_t it = (size_t)blockIdx.x * NT + threadIdx.x; it < total; it += (size_t)gridDim.x * NT) {
+    const int x = (int)(it % W), r = (int)((it / W) % rb);
+    const size_t pl = it / ((size_t)W * rb);
+    const int c = (int)(pl % C), z = (int)(pl / C);
+    out[(pl * H + y0 + r) * W + x] = anyvol[c] ? slice_min(d2band + ((size_t)c * rb + r) * W + x, stride, N, z, s) : DIST_NONE;
+  }
+}
+
+// ---- slice-axis pass of a band at the query voxels: a workgroup per 256 voxels of one pair.  keys (with offsets, cursor, capacity, overflow)
+// and / or minout
+__global__ __launch_bounds__(NT) void dist_query3_kernel(const u64* __restrict__ qbits, const int* __restrict__ d2band, const int* __restrict__ anyvol,
+                                                         int N, BitGeo g, int Ca, int Cb, const int* __restrict__ pairs, int P, int y0, int rb, int s,
+                                                         long long seg0, const long long* __restrict__ offsets, u64* __restrict__ cursor,
+                                                         long long* __restrict__ keys, long long capacity, int* __restrict__ overflow,
+                                                         u64* __restrict__ minout) {
+  const size_t per = (size_t)N * rb * g.W, chunks = (per + NT - 1) / NT, total = chunks * P, stride = (size_t)Cb * rb * g.W;
+  const int lane = threadIdx.x & 63;
+  for (size_t ch = blockIdx.x; ch < total; ch += gridDim.x) {      // workgroup-uniform: every lane takes part in the ballots and shuffles
+    const int p = (int)(ch / chunks);
+    const size_t i = (ch % chunks) * NT + threadIdx.x;
+    const int ca = min(max(pairs[2 * p], 0), Ca - 1), cb = min(max(pairs[2 * p + 1], 0), Cb - 1);
+    bool q = false;
+    int d = DIST_NONE;
+    unsigned voxel = 0u;
+    if (i < per) {
+      const int x = (int)(i % g.W), r = (int)((i / g.W) % rb), z = (int)(i / ((size_t)g.W * rb)), y = y0 + r;
+      q = (qbits[(((size_t)z * Ca + ca) * g.H + y) * g.W64 + (x >> 6)] >> (x & 63)) & 1ull;
+      if (q && anyvol[cb]) d = slice_min(d2band + ((size_t)cb * rb + r) * g.W + x, stride, N, z, s);
+      voxel = (unsigned)((size_t)z * g.HW + (size_t)y * g.W + x);
+    }
+    if (keys) {
+      const u64 m = __ballot(q);
+      if (m) {                                                     // wave-uniform
+        const int leader = ctz64(m);
+        u64 base = 0ull;
+        if (lane == leader) base = atomicAdd(cursor + p, (u64)__popcll(m));
+        base = __shfl(base, leader, 64);
+        if (q) {
+          const long long pos = offsets[p] + (long long)(base + (u64)__popcll(m & ((1ull << lane) - 1ull)));
+          if (pos >= 0 && pos < capacity) keys[pos] = (long long)(((u64)(seg0 + p) << 32) | (u64)(unsigned)d);
+          else *overflow = 1;
+        }
+      }
+    }
+    if (minout) {
+      u64 best = q ? (((u64)(unsigned)d << 32) | (u64)voxel) : ~0ull;
+      for (int sft = 32; sft > 0; sft >>= 1) {
+        const u64 o = __shfl_xor(best, sft, 64);
+        best = o < best ? o : best;
+      }
+      if (lane == 0 && best != ~0ull) atomicMin(minout + p, best);
+    }
+  }
+}
+
+// ---- the per-slice counts of dist_count_kernel summed over the slices: out int64 [P][2], overlap int64 [P][3] (may be null)
+__global__ __launch_bounds__(NT) void dist_count_sum_kernel(const int* __restrict__ counts, const int* __restrict__ overlap, int N, int P,
+                                                            long long* __restrict__ outc, long long* __restrict__ outo) {
+  const size_t total = (size_t)P * 5;
+  for (size_t it = (size_t)blockIdx.x * NT + threadIdx.x; it < total; it += (size_t)gridDim.x * NT) {
+    const int p = (int)(it / 5), k = (int)(it % 5);
+    long long sum = 0;
+    for (int n = 0; n < N; ++n) sum += k < 2 ? counts[((size_t)n * P + p) * 2 + k] : overlap[((size_t)n * P + p) * 3 + k - 2];
+    if (k < 2) outc[(size_t)p * 2 + k] = sum;
+    else if (outo) outo[(size_t)p * 3 + k - 2] = sum;
+  }
+}
+
+namespace {
+
+struct Scratch3 {
+  u64 *rawa, *rawb, *qa, *tb, *cursor;
+  u16* g;
+  int *any, *anyvol, *cnt, *d2;
+  size_t bytes;
+};
+
+// one-stack calls: Cb = 0, pairs = 0 (the target planes are qa); rows = the rows of a band, 0 for the calls that take no distance
+Scratch3 carve3(void* base, size_t N, int H, int W, int Ca, int Cb, int pairs, int rows) {
+  Scratch3 s;
+  const size_t words = (size_t)H * (((size_t)W + 63) / 64), Ct = Cb ? Cb : Ca, band = N * Ct * rows * W;
+  Carver cv(base);
+  s.rawa = cv.take<u64>(N * Ca * words);
+  s.qa = cv.take<u64>(N * Ca * words);
+  s.rawb = cv.take<u64>(N * Cb * words);
+  s.tb = cv.take<u64>(N * Cb * words);
+  s.any = cv.take<int>(N * Ct);
+  s.anyvol = cv.take<int>(Ct);
+  s.cursor = cv.take<u64>((size_t)pairs);
+  s.cnt = cv.take<int>(N * (size_t)pairs * 5);
+  s.g = cv.take<u16>(band);
+  s.d2 = cv.take<int>(band);
+  s.bytes = cv.used;
+  return s;
+}
+
+hipError_t prepare_volume(const float* src, const float* dst, int N, const BitGeo& g, int Ca, int Cb, int src_part, int dst_part, const Scratch3& s,
+                          hipStream_t st) {
+  const size_t wa = (size_t)N * Ca * g.H * g.W64, wb = (size_t)N * Cb * g.H * g.W64;
+  launch_bits_pack(src, N, g, Ca, Ca, 1, s.rawa, st);
+  launch_bits_pack(dst, N, g, Cb, Cb, 1, s.rawb, st);
+  hipError_t e = hipMemsetAsync(s.any, 0, (size_t)N * Cb * sizeof(int), st);
+  if (e == hipSuccess) e = hipMemsetAsync(s.anyvol, 0, (size_t)Cb * sizeof(int), st);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(dist_part3_kernel, dim3(item_grid(wa)), dim3(NT), 0, st, s.rawa, s.qa, N, Ca, g, src_part, (int*)nullptr, (int*)nullptr);
+  hipLaunchKernelGGL(dist_part3_kernel, dim3(item_grid(wb)), dim3(NT), 0, st, s.rawb, s.tb, N, Cb, g, dst_part, s.any, s.anyvol);
+  return hipSuccess;
+}
+
+// the per-slice map of band y0 .. y0 + rb - 1 of the target planes into s.d2
+void launch_band(const u64* target, int P, const BitGeo& g, const Scratch3& s, int y0, int rb, hipStream_t st) {
+  BitGeo gb = g;
+  gb.H = rb;
+  gb.HW = rb * g.W;
+  hipLaunchKernelGGL(dist_column_band_kernel, dim3(item_grid((size_t)P * g.W)), dim3(NT), 0, st, target, P, g, s.any, y0, rb, s.g);
+  hipLaunchKernelGGL(dist_map_kernel, dim3(block_grid((size_t)P * rb)), dim3(NT), 0, st, s.g, s.any, P, gb, s.d2);
+}
+
+}  // namespace
+
+size_t volume_distance_scratch_bytes(size_t N, int H, int W, int Ca, int Cb, int pairs, int rows) {
+  return carve3(nullptr, N, H, W, Ca, Cb, pairs, rows).bytes;
+}
+
+// the most rows of a band (1 .. H) whose scratch fits `bytes`; 0 when a band of one row does not.  The need grows with the rows.
+int volume_distance_rows(size_t bytes, size_t N, int H, int W, int Ca, int Cb, int pairs) {
+  if (volume_distance_scratch_bytes(N, H, W, Ca, Cb, pairs, 1) > bytes) return 0;
+  int lo = 1, hi = H;
+  while (lo < hi) {
+    const int mid = lo + (hi - lo + 1) / 2;
+    if (volume_distance_scratch_bytes(N, H, W, Ca, Cb, pairs, mid) <= bytes) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+hipError_t launch_volume_boundary(const float* stack, int N, int H, int W, int C, void* scratch, float* out, hipStream_t st) {
+  const BitGeo g = bit_geo(1, H, W);
+  const Scratch3 s = carve3(scratch, N, H, W, C, 0, 0, 0);
+  launch_bits_pack(stack, N, g, C, C, 1, s.rawa, st);
+  hipLaunchKernelGGL(dist_part3_kernel, dim3(item_grid((size_t)N * C * g.H * g.W64)), dim3(NT), 0, st, s.rawa, s.qa, N, C, g, 2, (int*)nullptr,
+                     (int*)nullptr);
+  launch_bits_unpack(s.qa, N, g, C, C, 1, out, st);
+  return hipGetLastError();
+}
+
+hipError_t launch_volume_distance(const float* stack, int N, int H, int W, int C, int to, int slice_step, int rows, void* scratch, int* d2,
+                                  hipStream_t st) {
+  const BitGeo g = bit_geo(1, H, W);
+  const int P = N * C;
+  const Scratch3 s = carve3(scratch, N, H, W, C, 0, 0, rows);
+  launch_bits_pack(stack, N, g, C, C, 1, s.rawa, st);
+  hipError_t e = hipMemsetAsync(s.any, 0, (size_t)P * sizeof(int), st);
+  if (e == hipSuccess) e = hipMemsetAsync(s.anyvol, 0, (size_t)C * sizeof(int), st);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(dist_part3_kernel, dim3(item_grid((size_t)P * g.H * g.W64)), dim3(NT), 0, st, s.rawa, s.qa, N, C, g, to, s.any, s.anyvol);
+  for (int y0 = 0; y0 < H; y0 += rows) {
+    const int rb = std::min(rows, H - y0);
+    launch_band(s.qa, P, g, s, y0, rb, st);
+    hipLaunchKernelGGL(dist_slice_map_kernel, dim3(item_grid((size_t)P * rb * W)), dim3(NT), 0, st, s.d2, s.anyvol, N, C, H, W, y0, rb, slice_step, d2);
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_volume_pair_counts(const float* src, const float* dst, int N, int H, int W, int Ca, int Cb, const int* pairs, int P, int src_part,
+                                     int dst_part, void* scratch, long long* counts, long long* overlap, hipStream_t st) {
+  const BitGeo g = bit_geo(1, H, W);
+  const Scratch3 s = carve3(scratch, N, H, W, Ca, Cb, P, 0);
+  hipError_t e = prepare_volume(src, dst, N, g, Ca, Cb, src_part, dst_part, s, st);
+  if (e != hipSuccess) return e;
+  int* over = s.cnt + (size_t)N * P * 2;
+  hipLaunchKernelGGL(dist_count_kernel, dim3(block_grid((size_t)N * P)), dim3(NT), 0, st, s.rawa, s.rawb, s.qa, s.tb, N, g, Ca, Cb, pairs, P, s.cnt, over);
+  hipLaunchKernelGGL(dist_count_sum_kernel, dim3(item_grid((size_t)P * 5)), dim3(NT), 0, st, s.cnt, over, N, P, counts, overlap);
+  return hipGetLastError();
+}
+
+// keys and / or minout (the other null)
+hipError_t launch_volume_pair_query(const float* src, const float* dst, int N, int H, int W, int Ca, int Cb, const int* pairs, int P, int src_part,
+                                    int dst_part, int slice_step, int rows, void* scratch, long long seg0, const long long* offsets, long long* keys,
+                                    long long capacity, int* overflow, unsigned long long* minout, hipStream_t st) {
+  const BitGeo g = bit_geo(1, H, W);
+  const Scratch3 s = carve3(scratch, N, H, W, Ca, Cb, P, rows);
+  hipError_t e = prepare_volume(src, dst, N, g, Ca, Cb, src_part, dst_part, s, st);
+  if (e == hipSuccess && keys) e = hipMemsetAsync(s.cursor, 0, (size_t)P * sizeof(u64), st);
+  if (e == hipSuccess && minout) e = hipMemsetAsync(minout, 0xFF, (size_t)P * sizeof(unsigned long long), st);
+  if (e != hipSuccess) return e;
+  for (int y0 = 0; y0 < H; y0 += rows) {
+    const int rb = std::min(rows, H - y0);
+    launch_band(s.tb, N * Cb, g, s, y0, rb, st);
+    const size_t chunks = ((size_t)N * rb * W + NT - 1) / NT * P;
+    hipLaunchKernelGGL(dist_query3_kernel, dim3(block_grid(chunks)), dim3(NT), 0, st, s.qa, s.d2, s.anyvol, N, g, Ca, Cb, pairs, P, y0, rb, slice_step,
+                       seg0, offsets, s.cursor, keys, capacity, overflow, (u64*)minout);
+  }
   return hipGetLastError();
 }
 

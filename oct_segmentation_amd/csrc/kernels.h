@@ -435,6 +435,20 @@ hipError_t launch_pair_distance_counts(const float* src, const float* dst, int N
 hipError_t launch_pair_distance_query(const float* src, const float* dst, int N, int H, int W, int Ca, int Cb, const int* pairs, int P, int src_part,
                                       int dst_part, void* scratch, long long seg0, const long long* offsets, long long* keys, long long capacity,
                                       int* overflow, unsigned long long* minout, hipStream_t st);
+// the same over the volume a channel's N planes form, slices slice_step pixels apart (distance.hip): the 6-neighbour boundary,
+// the per-slice map of a band of `rows` rows of all slices plus a pass along the slice axis, band after band; a segment is a pair, counts are
+// int64 [P][2] / [P][3].  scratch: volume_distance_scratch_bytes(N, H, W, Ca, Cb, pairs, rows) device bytes, rows = 0 for boundary and counts;
+// volume_distance_rows: the most rows (1 .. H) that fit `bytes`, 0 when one row does not
+size_t volume_distance_scratch_bytes(size_t N, int H, int W, int Ca, int Cb, int pairs, int rows);
+int volume_distance_rows(size_t bytes, size_t N, int H, int W, int Ca, int Cb, int pairs);
+hipError_t launch_volume_boundary(const float* stack, int N, int H, int W, int C, void* scratch, float* out, hipStream_t st);
+hipError_t launch_volume_distance(const float* stack, int N, int H, int W, int C, int to, int slice_step, int rows, void* scratch, int* d2,
+                                  hipStream_t st);
+hipError_t launch_volume_pair_counts(const float* src, const float* dst, int N, int H, int W, int Ca, int Cb, const int* pairs, int P, int src_part,
+                                     int dst_part, void* scratch, long long* counts, long long* overlap, hipStream_t st);
+hipError_t launch_volume_pair_query(const float* src, const float* dst, int N, int H, int W, int Ca, int Cb, const int* pairs, int P, int src_part,
+                                    int dst_part, int slice_step, int rows, void* scratch, long long seg0, const long long* offsets, long long* keys,
+                                    long long capacity, int* overflow, unsigned long long* minout, hipStream_t st);
 
 // raw pullback volumes (volume.hip): per-slice min / max + cv2.normalize(NORM_MINMAX, CV_8U) + channel order into uint8 [S][H][W][3] (one init,
 // two launches), and Pillow's 8-bit two-pass resample from host tables (a launch per axis that changes length; a copy when none does)
