@@ -60,6 +60,9 @@
  *                                      (no reference counterpart) the same over the volume the slices form, slice_step pixels apart: the
  *                                      6-neighbour boundary, exact 3-D squared distance maps in bands of rows, the volumetric HD / HD95 / ASSD
  *                                      lists per pair of channels, the smallest distance across slices with its voxel
+ *   octseg_stack_skeleton / octseg_skeleton_scratch_bytes
+ *                                      (no reference counterpart) the centreline of every mask plane by Guo and Hall's parallel thinning and its
+ *                                      census: set and skeleton pixels, end, junction and isolated points, passes
  *   octseg_volume_components / octseg_volume_cleanup / octseg_lesions_scratch_bytes
  *                                      (no reference counterpart) the connected components of a mask stack across its slices: labels, the 32
  *                                      largest lesions per class with their extents, the per-slice area profile, the flicker filter
@@ -670,6 +673,36 @@ int octseg_volume_pair_distance_keys(const float* src, const float* dst, int N, 
 int octseg_volume_pair_distance_min(const float* src, const float* dst, int N, int H, int W, int channels_a, int channels_b, const int* pairs, int npairs,
                                     int src_part, int dst_part, int slice_step, void* scratch, size_t scratch_bytes, unsigned long long* out,
                                     void* stream);
+
+/* Centrelines by thinning (no reference counterpart: the reference measures thickness along rays only; DESIGN.md section 5q, pinned by
+ * tests/skeleton_ref.py).  stack: device f32 [N][H][W][channels], any value != 0 is set; a plane is one (slice, channel) pair and every pixel
+ * outside the frame is clear.  Neighbours of pixel (y, x), clockwise from north:
+ *   P2 (y-1, x)  P3 (y-1, x+1)  P4 (y, x+1)  P5 (y+1, x+1)  P6 (y+1, x)  P7 (y+1, x-1)  P8 (y, x-1)  P9 (y-1, x-1)
+ * The SKELETON of a plane is Guo and Hall's two-sub-iteration parallel thinning (1989, algorithm A1).  With booleans as 0 / 1:
+ *   C  = (!P2 & (P3|P4)) + (!P4 & (P5|P6)) + (!P6 & (P7|P8)) + (!P8 & (P9|P2))
+ *   N1 = (P9|P2) + (P3|P4) + (P5|P6) + (P7|P8)
+ *   N2 = (P2|P3) + (P4|P5) + (P6|P7) + (P8|P9)
+ *   m  = sub-iteration 0: (P6 | P7 | !P9) & P8        sub-iteration 1: (P2 | P3 | !P5) & P4
+ *   a set pixel is deleted iff  C == 1  and  2 <= min(N1, N2) <= 3  and  m == 0
+ * Every deletion of a sub-iteration is decided on the plane as it stood when the sub-iteration began, then applied at once.  A PASS is
+ * sub-iteration 0 then sub-iteration 1; thinning ends after the first pass in which neither deletes anything; `passes` is the number of passes that
+ * deleted at least one pixel (0 for an empty or already thin plane).  The result is unique: results EQUAL the restatement's.  It keeps the number
+ * of 8-connected components and of holes; a 2 x 2 square thins to one pixel.
+ * octseg_stack_skeleton: out (may be NULL) f32 [N][H][W][channels], 0.0 / 1.0, must not alias stack = the skeleton of every plane;
+ *   census (may be NULL) int32 [N][channels][6] = set pixels, skeleton pixels, END points (skeleton pixels with exactly one of their 8 neighbours on
+ *   the skeleton), JUNCTION pixels (three or more), ISOLATED pixels (none), passes.  One workgroup thins one plane in one launch: from LDS when
+ *   the plane's H * ceil(W / 64) words fit it (up to 1024 x 1024 and beyond: 20478 words), else, or with flags bit 0 (OCTSEG_SKEL_GLOBAL) at any size,
+ *   over images in scratch; both give the same result.  The width of an object at its centreline is not computed here: it is
+ *   octseg_pair_distance_keys with src = out, dst = stack, src_part 0, dst_part 1 (the squared distance to the nearest clear pixel inside the frame).
+ * scratch: device, 8-byte aligned, scratch_bytes >= octseg_skeleton_scratch_bytes(N, H, W, channels) (three sets of bit planes, 1/8 byte per pixel
+ * and plane each; 0 is returned for extents the call refuses).
+ * Enqueue only, nothing is allocated.  Null stack or scratch, out and census both NULL, out == stack, scratch too small or misaligned, flag bits
+ * other than bit 0: OCTSEG_BAD_ARG; N, H, W <= 0, H or W above 4096, channels outside 1..16, N * channels * 6 reaching 2^31: OCTSEG_BAD_SHAPE.
+ * Nothing is launched then. */
+#define OCTSEG_SKEL_GLOBAL 1
+size_t octseg_skeleton_scratch_bytes(int N, int H, int W, int channels);
+int octseg_stack_skeleton(const float* stack, int N, int H, int W, int channels, int flags, void* scratch, size_t scratch_bytes,
+                          float* out /* [N][H][W][channels] 0.0 / 1.0, may be NULL */, int* census /* [N][channels][6], may be NULL */, void* stream);
 
 /* The arithmetic between a DICOM's pixel_array and the frames the pipeline takes (reference src/data/convert_dicoms.py:71-81, repeated in
  * src/app/tools/analysis.py:167-177): per slice cv2.normalize(img, None, alpha=0, beta=255, norm_type=NORM_MINMAX, dtype=CV_8U), then

@@ -187,6 +187,9 @@ SYMBOLS = {
     'octseg_volume_pair_distance_keys': (C.c_int, [_P, _P] + [C.c_int] * 5 + [_P] + [C.c_int] * 4 + [_P, C.c_size_t, C.c_longlong, _P, _P,
                                                    C.c_longlong, _P, _P]),
     'octseg_volume_pair_distance_min': (C.c_int, [_P, _P] + [C.c_int] * 5 + [_P] + [C.c_int] * 4 + [_P, C.c_size_t, _P, _P]),
+    # float32 mask stack -> the skeleton of every plane (Guo-Hall thinning, one workgroup per plane) and its census (csrc/skeleton.hip)
+    'octseg_skeleton_scratch_bytes': (C.c_size_t, [C.c_int] * 4),
+    'octseg_stack_skeleton': (C.c_int, [_P] + [C.c_int] * 5 + [_P, C.c_size_t, _P, _P, _P]),
     # raw volume [S,H,W,C] uint8 | uint16 -> per-slice min / max + uint8 RGB frames; Pillow's 8-bit bicubic resize from tables (csrc/volume.hip)
     'octseg_volume_normalize': (C.c_int, [_P] + [C.c_int] * 6 + [_P, _P, _P]),
     'octseg_resize_pil_u8': (C.c_int, [_P] + [C.c_int] * 4 + [_P, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, C.c_int, _P]),

@@ -450,6 +450,14 @@ hipError_t launch_volume_pair_query(const float* src, const float* dst, int N, i
                                     int dst_part, int slice_step, int rows, void* scratch, long long seg0, const long long* offsets, long long* keys,
                                     long long capacity, int* overflow, unsigned long long* minout, hipStream_t st);
 
+// centrelines (skeleton.hip): Guo and Hall's thinning of every plane by one workgroup per plane, all passes in one launch -- from
+// LDS when skeleton_fits_lds(H, W) and force_global == 0, else over ping-pong images in scratch --, and the census int32 [N][C][6] = set, skeleton,
+// end, junction, isolated pixels, passes.  scratch: skeleton_scratch_bytes(N, H, W, C) device bytes; out / census are optional (null = skipped)
+size_t skeleton_scratch_bytes(size_t N, int H, int W, int C);
+bool skeleton_fits_lds(int H, int W);
+hipError_t launch_stack_skeleton(const float* stack, int N, int H, int W, int C, int force_global, void* scratch, float* out, int* census,
+                                 hipStream_t st);
+
 // raw pullback volumes (volume.hip): per-slice min / max + cv2.normalize(NORM_MINMAX, CV_8U) + channel order into uint8 [S][H][W][3] (one init,
 // two launches), and Pillow's 8-bit two-pass resample from host tables (a launch per axis that changes length; a copy when none does)
 hipError_t launch_volume_normalize(const void* src, int src_u16, int S, int H, int W, int C, int swap_rb, unsigned* minmax, uint8_t* dst,

@@ -301,6 +301,8 @@ def _main_volume(cfg, device, dtypes, log):
         _save_plaque(res.plaque, res.stack, cfg['classes'], save_dir)
     if bool(cfg.get('lesions', False)):
         _save_lesions(res.stack, names, save_dir)
+    if bool(cfg.get('medial', False)):
+        _save_medial(res.stack, names, save_dir)
     if res.lumen is not None:
         _save_lumen(res.lumen, save_dir)
     if bool(cfg.get('contours', False)):
@@ -325,6 +327,13 @@ def _save_lesions(stack, names, save_dir):
     from .lesions import lesion_report
     with open(os.path.join(save_dir, 'lesions.json'), 'w') as f:
         json.dump(lesion_report(stack, names), f)
+
+
+def _save_medial(stack, names, save_dir):
+    """``medial=true``: ``{save_dir}/medial_thickness.json``, ``skeleton.thickness_report`` of the stack, slices in the order given."""
+    from .skeleton import thickness_report
+    with open(os.path.join(save_dir, 'medial_thickness.json'), 'w') as f:
+        json.dump(thickness_report(stack, names=names), f)
 
 
 def _save_plaque(report, stack, classes, save_dir):
@@ -390,6 +399,8 @@ def main(argv=None):
     arc, cap thickness where lipid lies behind it), and ``plaque_carpet.png`` (``polar.carpet_view``), slices in the order ``analysis`` uses;
     ``lesions`` (default false): also write ``{save_dir}/lesions.json``, the 3-D lesion report of the same stack (``lesions.lesion_report``:
     components across the slices, their length, voxels, bounding box and area profile), slices in the order ``analysis`` uses;
+    ``medial`` (default false): also write ``{save_dir}/medial_thickness.json``, the thickness of every class across its own centreline
+    (``skeleton.thickness_report``: skeleton pixels, end and junction points, width statistics per slice), slices in the order ``analysis`` uses;
     ``lumen`` (default false): also write ``{save_dir}/lumen.json``, the lumen report of the same stack (``shape.lumen_report``: lumen area and
     the diameters through the lumen's own centroid per frame, the minimal-lumen-area frame, percent area stenosis), slices in the order
     ``analysis`` uses;
@@ -474,6 +485,9 @@ def main(argv=None):
     if bool(cfg.get('lesions', False)):
         order = sorted(range(len(paths)), key=lambda i: os.path.basename(paths[i]))
         _save_lesions(stack[torch.tensor(order, device=stack.device)], [names[i] for i in order], str(cfg['save_dir']))
+    if bool(cfg.get('medial', False)):
+        order = sorted(range(len(paths)), key=lambda i: os.path.basename(paths[i]))
+        _save_medial(stack[torch.tensor(order, device=stack.device)], [names[i] for i in order], str(cfg['save_dir']))
     if bool(cfg.get('lumen', False)):
         from .shape import lumen_report
         order = sorted(range(len(paths)), key=lambda i: os.path.basename(paths[i]))
