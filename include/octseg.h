@@ -63,6 +63,9 @@
  *   octseg_stack_skeleton / octseg_skeleton_scratch_bytes
  *                                      (no reference counterpart) the centreline of every mask plane by Guo and Hall's parallel thinning and its
  *                                      census: set and skeleton pixels, end, junction and isolated points, passes
+ *   octseg_stack_prune / octseg_prune_scratch_bytes
+ *                                      (no reference counterpart) that centreline pruned: spurs removed, ends trimmed, a component that would
+ *                                      vanish restored; tips, end and junction points, orthogonal and diagonal links (the arc length)
  *   octseg_volume_components / octseg_volume_cleanup / octseg_lesions_scratch_bytes
  *                                      (no reference counterpart) the connected components of a mask stack across its slices: labels, the 32
  *                                      largest lesions per class with their extents, the per-slice area profile, the flicker filter
@@ -703,6 +706,46 @@ int octseg_volume_pair_distance_min(const float* src, const float* dst, int N, i
 size_t octseg_skeleton_scratch_bytes(int N, int H, int W, int channels);
 int octseg_stack_skeleton(const float* stack, int N, int H, int W, int channels, int flags, void* scratch, size_t scratch_bytes,
                           float* out /* [N][H][W][channels] 0.0 / 1.0, may be NULL */, int* census /* [N][channels][6], may be NULL */, void* stream);
+
+/* Centreline pruning (no reference counterpart; DESIGN.md section 5r, pinned by tests/prune_ref.py).  skel: device f32 [N][H][W][channels], any
+ * value != 0 is set; a plane is one (slice, channel) pair, every pixel outside the frame is clear, P2 .. P9 are the neighbours above.  The input is
+ * meant to be a skeleton (octseg_stack_skeleton's out); any plane is legal and the rules hold for any plane.  Only integers and booleans appear.
+ * A set pixel is a TIP when one of these holds (the eight end-point structuring elements of morphological pruning, Gonzalez and Woods):
+ *   orthogonal form, for one of the four orthogonal directions d: the neighbour at d is set and the five neighbours other than d and d's two
+ *   adjacent diagonals are all clear --
+ *     north  P2 & ~(P4|P5|P6|P7|P8)      east   P4 & ~(P6|P7|P8|P9|P2)      south  P6 & ~(P8|P9|P2|P3|P4)      west   P8 & ~(P2|P3|P4|P5|P6)
+ *   diagonal form: no orthogonal neighbour is set and exactly one diagonal neighbour is set.
+ * An isolated pixel is not a tip.  A tip is not the census's END point ("exactly one neighbour"): a one-pixel stub standing on a row has three
+ * neighbours, is a tip, and is no END.
+ *   erode(X, n)    repeats X <- X \ tips(X) n times, all tips of a pass decided on X as the pass found it; it stops early at the first pass
+ *                  without a tip
+ *   grow(D, n, A)  repeats D <- D | (dil8(D) & A) n times, dil8 the 3 x 3 dilation
+ * For a plane A and integers spur >= 0, trim >= 0:
+ *   X = erode(A, spur)
+ *   Y = X | grow(tips(X), spur, A)        (spur == 0: Y = A)
+ *   Z = erode(Y, trim)
+ *   R = the union of the 8-connected components of A that meet Z
+ *   out = Z | (A & ~R)
+ * A side branch of at most spur pixels goes away, longer branches and the main ends are regrown to their full length, trim then takes that many
+ * pixels off every end that is left, and a component that this would erase is returned whole and unpruned.  out is a subset of A with the same
+ * numbers of 8-connected components and of holes; a ring has no tip and is returned as it is; (0, 0) is the identity.
+ * LINKS are counted on out: orth = the pairs of 4-adjacent set pixels; diag = the pairs of diagonally adjacent set pixels whose two common
+ * 4-neighbours are both clear (otherwise the two orthogonal links already connect them): w & E, w & S, w & SE & ~E & ~S, w & SW & ~W & ~S.  The
+ * length along the centreline is orth + sqrt(2) * diag, computed in float64 on the host.
+ * octseg_stack_prune: out (may be NULL) f32 [N][H][W][channels], 0.0 / 1.0, must not alias skel; census (may be NULL) int32 [N][channels][9] =
+ *   0 input pixels, 1 output pixels, 2 tips of the output, 3 END points of the output (exactly one of the 8 neighbours set), 4 JUNCTION pixels
+ *   (three or more), 5 ISOLATED pixels (none), 6 orth links, 7 diag links, 8 restored pixels |A & ~R|.  One workgroup prunes one plane in one
+ *   launch: from LDS when the plane's padded bit image fits it (as for octseg_stack_skeleton), else, or with flags bit 0 (OCTSEG_PRUNE_GLOBAL) at
+ *   any size, over images in scratch; both give the same result.
+ * scratch: device, 8-byte aligned, scratch_bytes >= octseg_prune_scratch_bytes(N, H, W, channels) (four sets of bit planes, 1/8 byte per pixel
+ * and plane each; 0 is returned for extents the call refuses).
+ * Enqueue only, nothing is allocated.  Null skel or scratch, out and census both NULL, out == skel, scratch too small or misaligned, flag bits
+ * other than bit 0, spur or trim outside 0..8192 (an interface bound that keeps every loop count small): OCTSEG_BAD_ARG; N, H, W <= 0, H or W
+ * above 4096, channels outside 1..16, N * channels * 9 reaching 2^31: OCTSEG_BAD_SHAPE.  Nothing is launched then. */
+#define OCTSEG_PRUNE_GLOBAL 1
+size_t octseg_prune_scratch_bytes(int N, int H, int W, int channels);
+int octseg_stack_prune(const float* skel, int N, int H, int W, int channels, int spur, int trim, int flags, void* scratch, size_t scratch_bytes,
+                       float* out /* [N][H][W][channels] 0.0 / 1.0, may be NULL */, int* census /* [N][channels][9], may be NULL */, void* stream);
 
 /* The arithmetic between a DICOM's pixel_array and the frames the pipeline takes (reference src/data/convert_dicoms.py:71-81, repeated in
  * src/app/tools/analysis.py:167-177): per slice cv2.normalize(img, None, alpha=0, beta=255, norm_type=NORM_MINMAX, dtype=CV_8U), then

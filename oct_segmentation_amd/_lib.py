@@ -190,6 +190,9 @@ SYMBOLS = {
     # float32 mask stack -> the skeleton of every plane (Guo-Hall thinning, one workgroup per plane) and its census (csrc/skeleton.hip)
     'octseg_skeleton_scratch_bytes': (C.c_size_t, [C.c_int] * 4),
     'octseg_stack_skeleton': (C.c_int, [_P] + [C.c_int] * 5 + [_P, C.c_size_t, _P, _P, _P]),
+    # float32 skeleton stack -> every plane pruned (spurs removed, ends trimmed, vanished components restored) and its census (csrc/prune.hip)
+    'octseg_prune_scratch_bytes': (C.c_size_t, [C.c_int] * 4),
+    'octseg_stack_prune': (C.c_int, [_P] + [C.c_int] * 7 + [_P, C.c_size_t, _P, _P, _P]),
     # raw volume [S,H,W,C] uint8 | uint16 -> per-slice min / max + uint8 RGB frames; Pillow's 8-bit bicubic resize from tables (csrc/volume.hip)
     'octseg_volume_normalize': (C.c_int, [_P] + [C.c_int] * 6 + [_P, _P, _P]),
     'octseg_resize_pil_u8': (C.c_int, [_P] + [C.c_int] * 4 + [_P, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, C.c_int, _P]),

@@ -458,6 +458,15 @@ bool skeleton_fits_lds(int H, int W);
 hipError_t launch_stack_skeleton(const float* stack, int N, int H, int W, int C, int force_global, void* scratch, float* out, int* census,
                                  hipStream_t st);
 
+// centreline pruning (prune.hip): of every plane of a skeleton stack the side branches of at most `spur` pixels removed,
+// `trim` pixels taken off every end that is left, a component this would erase returned whole -- one workgroup per plane, all phases in one launch,
+// from LDS when skeleton_fits_lds(H, W) and force_global == 0, else over images in scratch --, and the census int32 [N][C][9] = input pixels, output
+// pixels, tips, end, junction, isolated points, orthogonal links, diagonal links, restored pixels.  scratch: prune_scratch_bytes(N, H, W, C)
+// device bytes; out / census are optional (null = skipped)
+size_t prune_scratch_bytes(size_t N, int H, int W, int C);
+hipError_t launch_stack_prune(const float* skel, int N, int H, int W, int C, int spur, int trim, int force_global, void* scratch, float* out,
+                              int* census, hipStream_t st);
+
 // raw pullback volumes (volume.hip): per-slice min / max + cv2.normalize(NORM_MINMAX, CV_8U) + channel order into uint8 [S][H][W][3] (one init,
 // two launches), and Pillow's 8-bit two-pass resample from host tables (a launch per axis that changes length; a copy when none does)
 hipError_t launch_volume_normalize(const void* src, int src_u16, int S, int H, int W, int C, int swap_rb, unsigned* minmax, uint8_t* dst,

@@ -302,7 +302,7 @@ def _main_volume(cfg, device, dtypes, log):
     if bool(cfg.get('lesions', False)):
         _save_lesions(res.stack, names, save_dir)
     if bool(cfg.get('medial', False)):
-        _save_medial(res.stack, names, save_dir)
+        _save_medial(res.stack, names, save_dir, int(cfg.get('medial_spur') or 0), int(cfg.get('medial_trim') or 0))
     if res.lumen is not None:
         _save_lumen(res.lumen, save_dir)
     if bool(cfg.get('contours', False)):
@@ -329,11 +329,15 @@ def _save_lesions(stack, names, save_dir):
         json.dump(lesion_report(stack, names), f)
 
 
-def _save_medial(stack, names, save_dir):
-    """``medial=true``: ``{save_dir}/medial_thickness.json``, ``skeleton.thickness_report`` of the stack, slices in the order given."""
+def _save_medial(stack, names, save_dir, spur=0, trim=0):
+    """``medial=true``: ``{save_dir}/medial_thickness.json``, ``skeleton.thickness_report`` of the stack, slices in the order given.  With
+    ``medial_spur`` or ``medial_trim`` above 0 the report is that of the pruned centreline and carries ``spur`` and ``trim`` at top level."""
     from .skeleton import thickness_report
+    report = thickness_report(stack, names=names, spur=spur, trim=trim)
+    if spur or trim:
+        report = {'spur': spur, 'trim': trim, **report}
     with open(os.path.join(save_dir, 'medial_thickness.json'), 'w') as f:
-        json.dump(thickness_report(stack, names=names), f)
+        json.dump(report, f)
 
 
 def _save_plaque(report, stack, classes, save_dir):
@@ -401,6 +405,9 @@ def main(argv=None):
     components across the slices, their length, voxels, bounding box and area profile), slices in the order ``analysis`` uses;
     ``medial`` (default false): also write ``{save_dir}/medial_thickness.json``, the thickness of every class across its own centreline
     (``skeleton.thickness_report``: skeleton pixels, end and junction points, width statistics per slice), slices in the order ``analysis`` uses;
+    ``medial_spur`` / ``medial_trim`` (default 0): the centreline is pruned first (``skeleton.prune_stack``: side branches of at most
+    ``medial_spur`` pixels removed, ``medial_trim`` pixels off every end that is left), the report gains ``tips``, ``length``, ``removed`` and
+    ``restored`` per class and carries ``spur`` and ``trim`` at top level;
     ``lumen`` (default false): also write ``{save_dir}/lumen.json``, the lumen report of the same stack (``shape.lumen_report``: lumen area and
     the diameters through the lumen's own centroid per frame, the minimal-lumen-area frame, percent area stenosis), slices in the order
     ``analysis`` uses;
@@ -487,7 +494,8 @@ def main(argv=None):
         _save_lesions(stack[torch.tensor(order, device=stack.device)], [names[i] for i in order], str(cfg['save_dir']))
     if bool(cfg.get('medial', False)):
         order = sorted(range(len(paths)), key=lambda i: os.path.basename(paths[i]))
-        _save_medial(stack[torch.tensor(order, device=stack.device)], [names[i] for i in order], str(cfg['save_dir']))
+        _save_medial(stack[torch.tensor(order, device=stack.device)], [names[i] for i in order], str(cfg['save_dir']),
+                     int(cfg.get('medial_spur') or 0), int(cfg.get('medial_trim') or 0))
     if bool(cfg.get('lumen', False)):
         from .shape import lumen_report
         order = sorted(range(len(paths)), key=lambda i: os.path.basename(paths[i]))
