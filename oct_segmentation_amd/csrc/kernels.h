@@ -451,8 +451,9 @@ hipError_t launch_volume_pair_query(const float* src, const float* dst, int N, i
                                     long long capacity, int* overflow, unsigned long long* minout, hipStream_t st);
 
 // centrelines (skeleton.hip): Guo and Hall's thinning of every plane by one workgroup per plane, all passes in one launch -- from
-// LDS when skeleton_fits_lds(H, W) and force_global == 0, else over ping-pong images in scratch --, and the census int32 [N][C][6] = set, skeleton,
-// end, junction, isolated pixels, passes.  scratch: skeleton_scratch_bytes(N, H, W, C) device bytes; out / census are optional (null = skipped)
+// the padded LDS image of planepass.h when skeleton_fits_lds(H, W) and force_global == 0, else over ping-pong images in scratch --, and the census
+// int32 [N][C][6] = set, skeleton, end, junction, isolated pixels, passes.  scratch: skeleton_scratch_bytes(N, H, W, C) device bytes; out / census
+// are optional (null = skipped)
 size_t skeleton_scratch_bytes(size_t N, int H, int W, int C);
 bool skeleton_fits_lds(int H, int W);
 hipError_t launch_stack_skeleton(const float* stack, int N, int H, int W, int C, int force_global, void* scratch, float* out, int* census,
@@ -460,9 +461,9 @@ hipError_t launch_stack_skeleton(const float* stack, int N, int H, int W, int C,
 
 // centreline pruning (prune.hip): of every plane of a skeleton stack the side branches of at most `spur` pixels removed,
 // `trim` pixels taken off every end that is left, a component this would erase returned whole -- one workgroup per plane, all phases in one launch,
-// from LDS when skeleton_fits_lds(H, W) and force_global == 0, else over images in scratch --, and the census int32 [N][C][9] = input pixels, output
-// pixels, tips, end, junction, isolated points, orthogonal links, diagonal links, restored pixels.  scratch: prune_scratch_bytes(N, H, W, C)
-// device bytes; out / census are optional (null = skipped)
+// from the padded LDS image of planepass.h when skeleton_fits_lds(H, W) and force_global == 0, else over images in scratch --, and the census
+// int32 [N][C][9] = input pixels, output pixels, tips, end, junction, isolated points, orthogonal links, diagonal links, restored pixels.  scratch:
+// prune_scratch_bytes(N, H, W, C) device bytes; out / census are optional (null = skipped)
 size_t prune_scratch_bytes(size_t N, int H, int W, int C);
 hipError_t launch_stack_prune(const float* skel, int N, int H, int W, int C, int spur, int trim, int force_global, void* scratch, float* out,
                               int* census, hipStream_t st);

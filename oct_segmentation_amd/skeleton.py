@@ -75,7 +75,7 @@ LDS_WORDS = (160 * 1024 - 16) // 8
 
 def fits_lds(h, w):
     """Whether ``path='auto'`` thins an ``h`` x ``w`` plane from LDS: its padded bit image, ``(h + 2) * (ceil(w / 64) + 1) + 1`` 64-bit words,
-    within the 160 KiB less the flags (``csrc/skeleton.hip``, ``lds_image_words``)."""
+    within the 160 KiB less the flags (``csrc/planepass.h``, ``lds_image_words``)."""
     return (int(h) + 2) * ((int(w) + 63) // 64 + 1) + 1 <= LDS_WORDS
 
 
@@ -85,22 +85,30 @@ def _flags(path):
     return PATHS[path]
 
 
+def _chunked(size_fn, n, h, w, sc, scratch_bytes, device, call):
+    """``call(i, m, scratch, need)`` for every chunk of ``m`` slices from slice ``i``: as many slices as ``scratch_bytes`` holds by ``size_fn(slices,
+    h, w, sc)``, one at least; the scratch block of ``need`` bytes is allocated once."""
+    with torch.cuda.device(device):
+        per_slice = int(size_fn(1, h, w, sc))
+        step = max(min(n, int(scratch_bytes) // per_slice), 1)
+        need = int(size_fn(step, h, w, sc))
+        scratch = torch.empty((need,), dtype=torch.uint8, device=device)
+        for i in range(0, n, step):
+            call(i, min(step, n - i), scratch, need)
+
+
 def _run(stack, want_out, want_census, path, scratch_bytes):
     flags = _flags(path)
     stack, n, h, w, sc = distance._check(stack)
     out = torch.empty_like(stack) if want_out else None
     census = torch.empty((n, sc, 6), dtype=torch.int32, device=stack.device) if want_census else None
     lib = L.lib()
-    with torch.cuda.device(stack.device):
-        per_slice = int(lib.octseg_skeleton_scratch_bytes(1, h, w, sc))
-        step = max(min(n, int(scratch_bytes) // per_slice), 1)
-        need = int(lib.octseg_skeleton_scratch_bytes(step, h, w, sc))
-        scratch = torch.empty((need,), dtype=torch.uint8, device=stack.device)
-        for i in range(0, n, step):
-            m = min(step, n - i)
-            L.check(lib.octseg_stack_skeleton(L.ptr(stack[i:i + m]), m, h, w, sc, flags, L.ptr(scratch), need,
-                                              L.ptr(out[i:i + m]) if want_out else None, L.ptr(census[i:i + m]) if want_census else None,
-                                              L.stream_ptr()))
+
+    def call(i, m, scratch, need):
+        L.check(lib.octseg_stack_skeleton(L.ptr(stack[i:i + m]), m, h, w, sc, flags, L.ptr(scratch), need,
+                                          L.ptr(out[i:i + m]) if want_out else None, L.ptr(census[i:i + m]) if want_census else None,
+                                          L.stream_ptr()))
+    _chunked(lib.octseg_skeleton_scratch_bytes, n, h, w, sc, scratch_bytes, stack.device, call)
     return out, census
 
 
@@ -140,15 +148,11 @@ def prune_stack(skel, spur=0, trim=0, with_census=False, path='auto', scratch_by
     out = torch.empty_like(skel)
     census = torch.empty((n, sc, 9), dtype=torch.int32, device=skel.device) if with_census else None
     lib = L.lib()
-    with torch.cuda.device(skel.device):
-        per_slice = int(lib.octseg_prune_scratch_bytes(1, h, w, sc))
-        step = max(min(n, int(scratch_bytes) // per_slice), 1)
-        need = int(lib.octseg_prune_scratch_bytes(step, h, w, sc))
-        scratch = torch.empty((need,), dtype=torch.uint8, device=skel.device)
-        for i in range(0, n, step):
-            m = min(step, n - i)
-            L.check(lib.octseg_stack_prune(L.ptr(skel[i:i + m]), m, h, w, sc, spur, trim, flags, L.ptr(scratch), need, L.ptr(out[i:i + m]),
-                                           L.ptr(census[i:i + m]) if with_census else None, L.stream_ptr()))
+
+    def call(i, m, scratch, need):
+        L.check(lib.octseg_stack_prune(L.ptr(skel[i:i + m]), m, h, w, sc, spur, trim, flags, L.ptr(scratch), need, L.ptr(out[i:i + m]),
+                                       L.ptr(census[i:i + m]) if with_census else None, L.stream_ptr()))
+    _chunked(lib.octseg_prune_scratch_bytes, n, h, w, sc, scratch_bytes, skel.device, call)
     return (out, census) if with_census else out
 
 

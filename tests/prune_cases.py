@@ -127,3 +127,8 @@ def excerpt_skeleton():
 def sparse_skeleton(side, seed):
     """The skeleton of ``skeleton_cases.sparse_large``: strokes and small blobs, so both references stay fast."""
     return thinned(K.sparse_large(side, seed=seed))
+
+
+def ladder_skeleton(k):
+    """The skeleton of ``skeleton_cases.ladder_plane`` at the shape that selects the register-tile size ``k``."""
+    return thinned(K.ladder_plane(*K.LADDER_SHAPES[k]))

@@ -101,6 +101,42 @@ def sparse_large(side=1280, seed=5):
     return m
 
 
+# ---- one plane per register-tile size K of the LDS kernels: K -> (H, W).  owned = H * (ceil(W / 64) + 1) words over 1024 threads selects K, and
+# the padded image stays within the LDS limit.  Tall and narrow: the smallest planes that reach the high K
+LADDER = (1, 2, 4, 7, 10, 13, 17, 20)
+LADDER_SHAPES = {2: (300, 130), 4: (800, 130), 7: (1500, 130), 10: (2300, 130), 13: (3000, 130), 17: (4000, 130), 20: (3700, 200)}
+
+
+def ladder_k(h, w):
+    """The K the dispatch selects for an ``h`` x ``w`` plane with more than 1024 owned words."""
+    owned = h * ((w + 63) // 64 + 1)
+    assert owned > 1024
+    k = -(-owned // 1024)
+    return min(v for v in LADDER if v >= k)
+
+
+def ladder_plane(h, w, seed=3):
+    """3-pixel bars along the first and the last rows (the words a thread owns first and last, next to the pad rows), two dozen strokes 1 to 5
+    pixels thick, a 30 x 8 block across the column 63 / 64 seam: objects that thin in a few passes, so the reference stays fast."""
+    rng = np.random.RandomState(seed + 31 * h + w)
+    m = np.zeros((h, w), bool)
+    m[0:3, 4:w - 4] = True
+    m[h - 3:h, 4:w - 4] = True
+    for _ in range(24):
+        t = rng.randint(1, 6)
+        if rng.rand() < 0.5:
+            n = rng.randint(20, w - 20)
+            y, x = rng.randint(8, h - 8 - t), rng.randint(2, w - n - 2)
+            m[y:y + t, x:x + n] = True
+        else:
+            n = rng.randint(40, 250)
+            y, x = rng.randint(8, h - 8 - n), rng.randint(2, w - t - 2)
+            m[y:y + n, x:x + t] = True
+    y = h // 2
+    m[y:y + 30, 60:68] = True
+    return m
+
+
 # ---- the demo excerpt (tests/golden/pullback_demo_excerpt.npz): slices 28 - 30; channel = CLASS_IDS - 1
 LUMEN, CAP, LIPID, VASA = 0, 1, 2, 3
 EXCERPT_PLANES = [(28, CAP), (29, CAP), (30, CAP), (28, VASA), (29, VASA), (30, VASA), (29, LIPID), (29, LUMEN)]

@@ -156,6 +156,14 @@ def test_lds_path_at_1024(cuda):
     both_paths(s[None, :, :, None], 6, 10, cuda)
 
 
+@pytest.mark.parametrize('k', sorted(K.LADDER_SHAPES))
+def test_every_register_tile_size_of_the_lds_kernel(cuda, k):
+    """One skeleton per instantiation prune_lds_kernel<K> that no other shape here reaches: output and census on both paths."""
+    h, w = K.LADDER_SHAPES[k]
+    assert skeleton.fits_lds(h, w) and K.ladder_k(h, w) == k
+    both_paths(Q.ladder_skeleton(k)[None, :, :, None], 3, 5, cuda)
+
+
 def test_sparse_large_plane_takes_the_global_path(cuda):
     assert not skeleton.fits_lds(1280, 1280)
     s = Q.sparse_skeleton(1280, 5)

@@ -90,6 +90,14 @@ def test_lds_path_at_1024(cuda):
     both_paths(m[None, :, :, None], cuda)
 
 
+@pytest.mark.parametrize('k', sorted(K.LADDER_SHAPES))
+def test_every_register_tile_size_of_the_lds_kernel(cuda, k):
+    """One plane per instantiation skel_thin_lds_kernel<K> that no other shape here reaches: thinning, census and passes on both paths."""
+    h, w = K.LADDER_SHAPES[k]
+    assert skeleton.fits_lds(h, w) and K.ladder_k(h, w) == k
+    both_paths(K.ladder_plane(h, w)[None, :, :, None], cuda)
+
+
 # ---- 4. bounds
 def test_chunking_guard_bands_and_optional_outputs(cuda):
     st = np.stack([np.stack([K.blobs(33, 65, i * 4 + k) for k in range(4)], axis=-1) for i in range(3)])
