@@ -60,6 +60,9 @@
  *                                      (no reference counterpart) the same over the volume the slices form, slice_step pixels apart: the
  *                                      6-neighbour boundary, exact 3-D squared distance maps in bands of rows, the volumetric HD / HD95 / ASSD
  *                                      lists per pair of channels, the smallest distance across slices with its voxel
+ *   octseg_stack_signed_distance / octseg_signed_blend / octseg_signed_distance_scratch_bytes
+ *                                      (no reference counterpart) signed squared distance maps of the mask planes and the blend of two of them
+ *                                      by integer weights: slices interpolated between their neighbours, gaps bridged, stacks resampled
  *   octseg_stack_skeleton / octseg_skeleton_scratch_bytes
  *                                      (no reference counterpart) the centreline of every mask plane by Guo and Hall's parallel thinning and its
  *                                      census: set and skeleton pixels, end, junction and isolated points, passes
@@ -676,6 +679,34 @@ int octseg_volume_pair_distance_keys(const float* src, const float* dst, int N, 
 int octseg_volume_pair_distance_min(const float* src, const float* dst, int N, int H, int W, int channels_a, int channels_b, const int* pairs, int npairs,
                                     int src_part, int dst_part, int slice_step, void* scratch, size_t scratch_bytes, unsigned long long* out,
                                     void* stream);
+
+/* Slices interpolated from signed distance maps (no reference counterpart; shape-based interpolation after Raya and Udupa, DESIGN.md section 5s,
+ * pinned to scipy.ndimage by tests/interp_ref.py).  A plane is one (slice, channel) pair of the f32 stack [N][H][W][channels], any value != 0 set.
+ * The SIGNED SQUARED DISTANCE sd2, int32 in the layout [N][channels][H][W] that octseg_stack_distance writes:
+ *   at a set pixel    +d2 to the nearest clear pixel of the plane, so >= 1;
+ *   at a clear pixel  -d2 to the nearest set pixel, so <= -1;
+ *   on an empty plane -OCTSEG_DIST_NONE everywhere, on a full plane +OCTSEG_DIST_NONE everywhere; never 0
+ *   (= where(m, stack_distance(to = clear), -stack_distance(to = set))).
+ * The BLEND of planes a and b with integer weights 0 <= wa, wb <= 32767, not both 0: with s = sign(sd2) * sqrt(|sd2|), +-infinity for
+ * OCTSEG_DIST_NONE, a pixel is set iff wa * s_a + wb * s_b > 0.  The decision is made in integers only:
+ *   a weight of 0 removes its side and the other side's sign decides;
+ *   equal signs: that sign decides;
+ *   opposite signs, both finite: set iff wP^2 * |sd2_P| > wQ^2 * |sd2_Q| in int64 (below 2^55), P the positive and Q the negative side;
+ *   opposite signs, exactly one infinite: its sign decides;  both infinite: set iff wP > wQ;
+ *   a tie is clear.
+ * A PLAN is device int32 [M][6], rows (channel, out_slice, lo, hi, w_lo, w_hi): row r writes plane (out_slice, channel) of out f32
+ * [N_out][H][W][channels] as 0.0 / 1.0, the blend of planes (lo, channel) and (hi, channel) of sd2 (K slices) with weights w_lo and w_hi.  Planes
+ * that no row names are not touched; two rows that name one plane race (the wrappers refuse them).  Every number of a row is clamped on the device
+ * into its range: a wrong plan gives a wrong plane, never a stray access.  made (may be NULL) int32 [M] = the set pixels of each written plane.
+ * scratch: device, 8-byte aligned, scratch_bytes >= octseg_signed_distance_scratch_bytes(N, H, W, channels) (two sets of bit planes, 4 bytes per
+ * pixel and channel, the flags; 0 is returned for extents the calls refuse).
+ * Enqueue only, nothing is allocated, nothing synchronises.  Null pointer (made excepted), scratch too small or misaligned, sd2 == stack, out ==
+ * sd2: OCTSEG_BAD_ARG; extents <= 0, H or W above 4096, channels outside 1..16, M <= 0: OCTSEG_BAD_SHAPE.  Nothing is launched then.
+ * Out of scope: extrapolation, registration between slices (objects that do not overlap vanish), non-integer weights. */
+size_t octseg_signed_distance_scratch_bytes(int N, int H, int W, int channels);
+int octseg_stack_signed_distance(const float* stack, int N, int H, int W, int channels, void* scratch, size_t scratch_bytes, int* sd2, void* stream);
+int octseg_signed_blend(const int* sd2, int K, int H, int W, int channels, const int* plan, int M, float* out, int N_out, int* made /* may be NULL */,
+                        void* stream);
 
 /* Centrelines by thinning (no reference counterpart: the reference measures thickness along rays only; DESIGN.md section 5q, pinned by
  * tests/skeleton_ref.py).  stack: device f32 [N][H][W][channels], any value != 0 is set; a plane is one (slice, channel) pair and every pixel

@@ -187,6 +187,10 @@ SYMBOLS = {
     'octseg_volume_pair_distance_keys': (C.c_int, [_P, _P] + [C.c_int] * 5 + [_P] + [C.c_int] * 4 + [_P, C.c_size_t, C.c_longlong, _P, _P,
                                                    C.c_longlong, _P, _P]),
     'octseg_volume_pair_distance_min': (C.c_int, [_P, _P] + [C.c_int] * 5 + [_P] + [C.c_int] * 4 + [_P, C.c_size_t, _P, _P]),
+    # float32 mask stack -> signed squared distance maps; two of them + a plan of integer weights -> interpolated planes (csrc/distance.hip)
+    'octseg_signed_distance_scratch_bytes': (C.c_size_t, [C.c_int] * 4),
+    'octseg_stack_signed_distance': (C.c_int, [_P] + [C.c_int] * 4 + [_P, C.c_size_t, _P, _P]),
+    'octseg_signed_blend': (C.c_int, [_P] + [C.c_int] * 4 + [_P, C.c_int, _P, C.c_int, _P, _P]),
     # float32 mask stack -> the skeleton of every plane (Guo-Hall thinning, one workgroup per plane) and its census (csrc/skeleton.hip)
     'octseg_skeleton_scratch_bytes': (C.c_size_t, [C.c_int] * 4),
     'octseg_stack_skeleton': (C.c_int, [_P] + [C.c_int] * 5 + [_P, C.c_size_t, _P, _P, _P]),

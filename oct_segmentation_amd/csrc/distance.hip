@@ -2,7 +2,8 @@
 // the squared distance of every pixel to the nearest target pixel, the directed boundary-to-boundary distance lists behind the Hausdorff
 // family (HD, HD95, ASSD), the smallest distance between two classes with the pixel that attains it, and the overlap counts of the same
 // planes.  No reference counterpart: the reference reports overlap scores only (DESIGN.md section 5i states the definitions).  The second half of the
-// file does the same over the volume a channel's planes form (section 5p; its own comment below).
+// file does the same over the volume a channel's planes form (section 5p; its own comment below); the last section is the signed map and the
+// blend of two of them, shape-based interpolation between slices (section 5s; its own comment below).
 //
 // A plane is one (slice, channel) pair of the float32 stack [N][H][W][C], any value != 0 set.  Planes live as the bit planes of bitplanes.h, every
 // plane on its own (its geometry with D = 1); pack and unpack are the shared kernels of bitplanes.hip.  Everything is integer arithmetic on
@@ -616,6 +617,139 @@ hipError_t launch_volume_pair_query(const float* src, const float* dst, int N, i
     hipLaunchKernelGGL(dist_query3_kernel, dim3(block_grid(chunks)), dim3(NT), 0, st, s.qa, s.d2, s.anyvol, N, g, Ca, Cb, pairs, P, y0, rb, slice_step,
                        seg0, offsets, s.cursor, keys, capacity, overflow, (u64*)minout);
   }
+  return hipGetLastError();
+}
+
+// ==== SIGNED squared distance maps and their blend: shape-based interpolation between slices.  sd2 int32 [N][C][H][W]:
+// +d2 to the nearest clear pixel at a set pixel, -d2 to the nearest set pixel at a clear one, -/+ DIST_NONE on an empty / a full plane, never 0.
+//
+//   signed map  pack, then dist_part_kernel and dist_column_kernel as they are, once for part `set` and once for part `clear`, the second part
+//               written over the first (its columns are taken by then: launches of one stream): two sets of bits, two uint16 column maps, two
+//               sets of flags.  A workgroup per (plane, row) stages BOTH rows of g in LDS (2 x 8 KiB at most); a lane per pixel is set iff
+//               g_set[x] == 0 and runs ONE row_min, over the other part's row.  A plane either flag shows as empty is filled without a search;
+//               its g (which the column pass skipped) is never read.
+//   blend       a lane per pixel of every plan row (channel, out_slice, lo, hi, w_lo, w_hi): two int32 loads, the integer rule below, one
+//               float store of 0.0 / 1.0 into out [N_out][H][W][C].  Every workgroup lies inside one row, so a wave's set pixels are one
+//               popcount of a ballot and one atomic into made[row].  The row's six numbers are clamped: a wrong plan gives a wrong plane.
+//
+// TERMINATION: the only loop whose trip count depends on data is row_min's, bounded by W (k < W) whatever the row holds, and best only falls; the
+// grid-stride loops are bounded by their totals.  No workgroup waits on another: no spin, no flag, no cooperative launch; the only atomics are
+// integer adds into made, whose result nobody reads inside the launch.
+namespace {
+
+constexpr int MAX_WEIGHT = 32767;
+
+// wa * s_a + wb * s_b > 0 with s = sign(sd2) * sqrt(|sd2|), DIST_NONE infinite, decided in integers: a zero weight removes its side; equal signs
+// decide; of opposite signs the larger of w^2 * |sd2| (int64, below 2^30 * 2^25) decides, an infinite side beats a finite one, two infinite ones go
+// by the weights; a tie is clear
+__device__ __forceinline__ bool blend_set(int a, int b, int wa, int wb) {
+  if (wa == 0) return wb != 0 && b > 0;
+  if (wb == 0) return a > 0;
+  const bool pa = a > 0, pb = b > 0;
+  if (pa == pb) return pa;
+  const int p = pa ? a : b, q = pa ? b : a, wp = pa ? wa : wb, wq = pa ? wb : wa;   // p > 0 > q
+  const bool pinf = p == DIST_NONE, qinf = q == -DIST_NONE;
+  if (pinf || qinf) return pinf && (!qinf || wp > wq);
+  return (long long)wp * wp * p > (long long)wq * wq * -(long long)q;
+}
+
+struct ScratchS {
+  u64 *raw, *part;
+  u16 *gset, *gclear;
+  int* any;                                                          // [2][P]: set, clear; one memset
+  size_t bytes;
+};
+
+ScratchS carve_signed(void* base, size_t N, int H, int W, int C) {
+  ScratchS s;
+  const size_t P = N * C, HW = (size_t)H * W, words = (size_t)H * (((size_t)W + 63) / 64);
+  Carver cv(base);
+  s.raw = cv.take<u64>(P * words);
+  s.part = cv.take<u64>(P * words);
+  s.gset = cv.take<u16>(P * HW);
+  s.gclear = cv.take<u16>(P * HW);
+  s.any = cv.take<int>(2 * P);
+  s.bytes = cv.used;
+  return s;
+}
+
+}  // namespace
+
+// ---- signed map: a workgroup per (plane, row), both rows of g in LDS
+__global__ __launch_bounds__(NT) void dist_signed_map_kernel(const u16* __restrict__ gset, const u16* __restrict__ gclear, const int* __restrict__ anyset,
+                                                             const int* __restrict__ anyclear, int P, BitGeo g, int* __restrict__ sd2) {
+  __shared__ u16 rows[2][MAX_W];
+  const size_t total = (size_t)P * g.H;
+  for (size_t it = blockIdx.x; it < total; it += gridDim.x) {      // workgroup-uniform
+    const size_t pl = it / g.H;
+    int* out = sd2 + it * g.W;
+    const int hs = anyset[pl], hc = anyclear[pl];
+    if (!hs || !hc) {                                                // empty: every pixel clear and no set pixel to measure to; full: the reverse
+      const int v = hs ? DIST_NONE : -DIST_NONE;
+      for (int x = threadIdx.x; x < g.W; x += NT) out[x] = v;
+      continue;
+    }
+    const u16 *ss = gset + it * g.W, *sc = gclear + it * g.W;
+    for (int x = threadIdx.x; x < g.W; x += NT) { rows[0][x] = ss[x]; rows[1][x] = sc[x]; }
+    __syncthreads();
+    for (int x = threadIdx.x; x < g.W; x += NT) {
+      const bool set = rows[0][x] == 0;                              // the pixel's own bit: distance 0 to its own column's nearest set pixel
+      const int d = row_min(rows[set ? 1 : 0], g.W, x);              // both parts hold a pixel: finite and >= 1
+      out[x] = set ? d : -d;
+    }
+    __syncthreads();                                                 // the next row overwrites the stages
+  }
+}
+
+// ---- blend: workgroups [M][chunks of NT pixels]; plan int32 [M][6]; made (may be null) int32 [M], cleared by the caller
+__global__ __launch_bounds__(NT) void dist_blend_kernel(const int* __restrict__ sd2, int K, int HW, int C, const int* __restrict__ plan, int M,
+                                                        float* __restrict__ out, int Nout, int* __restrict__ made) {
+  const size_t chunks = ((size_t)HW + NT - 1) / NT, total = chunks * M;
+  const int lane = threadIdx.x & 63;
+  for (size_t it = blockIdx.x; it < total; it += gridDim.x) {      // workgroup-uniform: every lane takes part in the ballot
+    const size_t r = it / chunks;
+    const int* row = plan + r * 6;
+    const int c = min(max(row[0], 0), C - 1), os = min(max(row[1], 0), Nout - 1);
+    const int lo = min(max(row[2], 0), K - 1), hi = min(max(row[3], 0), K - 1);
+    const int wa = min(max(row[4], 0), MAX_WEIGHT), wb = min(max(row[5], 0), MAX_WEIGHT);
+    const size_t pix = (it % chunks) * NT + threadIdx.x;
+    bool set = false;
+    if (pix < (size_t)HW) {
+      set = blend_set(sd2[((size_t)lo * C + c) * HW + pix], sd2[((size_t)hi * C + c) * HW + pix], wa, wb);
+      out[((size_t)os * HW + pix) * C + c] = set ? 1.0f : 0.0f;
+    }
+    if (made) {
+      const u64 m = __ballot(set);
+      if (lane == 0 && m) atomicAdd(made + r, __popcll(m));
+    }
+  }
+}
+
+size_t signed_distance_scratch_bytes(size_t N, int H, int W, int C) { return carve_signed(nullptr, N, H, W, C).bytes; }
+
+hipError_t launch_stack_signed_distance(const float* stack, int N, int H, int W, int C, void* scratch, int* sd2, hipStream_t st) {
+  const BitGeo g = bit_geo(1, H, W);
+  const int P = N * C;
+  const ScratchS s = carve_signed(scratch, N, H, W, C);
+  const size_t words = (size_t)P * g.H * g.W64;
+  launch_bits_pack(stack, N, g, C, C, 1, s.raw, st);
+  hipError_t e = hipMemsetAsync(s.any, 0, (size_t)2 * P * sizeof(int), st);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(dist_part_kernel, dim3(item_grid(words)), dim3(NT), 0, st, s.raw, s.part, P, g, 0, s.any);
+  hipLaunchKernelGGL(dist_column_kernel, dim3(item_grid((size_t)P * g.W)), dim3(NT), 0, st, s.part, P, g, s.any, s.gset);
+  hipLaunchKernelGGL(dist_part_kernel, dim3(item_grid(words)), dim3(NT), 0, st, s.raw, s.part, P, g, 1, s.any + P);
+  hipLaunchKernelGGL(dist_column_kernel, dim3(item_grid((size_t)P * g.W)), dim3(NT), 0, st, s.part, P, g, s.any + P, s.gclear);
+  hipLaunchKernelGGL(dist_signed_map_kernel, dim3(block_grid((size_t)P * g.H)), dim3(NT), 0, st, s.gset, s.gclear, s.any, s.any + P, P, g, sd2);
+  return hipGetLastError();
+}
+
+hipError_t launch_signed_blend(const int* sd2, int K, int H, int W, int C, const int* plan, int M, float* out, int Nout, int* made, hipStream_t st) {
+  if (made) {
+    const hipError_t e = hipMemsetAsync(made, 0, (size_t)M * sizeof(int), st);
+    if (e != hipSuccess) return e;
+  }
+  const size_t chunks = ((size_t)H * W + NT - 1) / NT;
+  hipLaunchKernelGGL(dist_blend_kernel, dim3(block_grid(chunks * M)), dim3(NT), 0, st, sd2, K, H * W, C, plan, M, out, Nout, made);
   return hipGetLastError();
 }
 

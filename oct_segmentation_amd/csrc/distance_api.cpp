@@ -1,5 +1,6 @@
 // distance_api.cpp -- the C ABI of the boundary-distance kernels (distance.hip; no reference counterpart): argument checks in
-// front of the launchers.  Enqueue only; every refusal happens before anything is launched.
+// front of the launchers.  Enqueue only; every refusal happens before anything is launched.  The volume calls (section 5p) and the signed maps with
+// their blend (section 5s) follow in sections of their own.
 #include "plan_internal.h"
 
 using namespace octseg;
@@ -200,6 +201,40 @@ int octseg_volume_pair_distance_min(const float* src, const float* dst, int N, i
     return rc;
   HIPCHK(launch_volume_pair_query(src, dst, N, H, W, channels_a, channels_b, pairs, npairs, src_part, dst_part, slice_step, rows, scratch, 0, nullptr,
                                   nullptr, 0, nullptr, out, (hipStream_t)stream));
+  return OCTSEG_OK;
+}
+
+}  // extern "C"
+
+// ---- signed maps and their blend
+extern "C" {
+
+size_t octseg_signed_distance_scratch_bytes(int N, int H, int W, int channels) {
+  if (!extents_ok(N, H, W) || channels <= 0 || channels > MAX_CH) return 0;
+  return signed_distance_scratch_bytes((size_t)N, H, W, channels);
+}
+
+int octseg_stack_signed_distance(const float* stack, int N, int H, int W, int channels, void* scratch, size_t scratch_bytes, int* sd2, void* stream) {
+  if (!stack || !scratch || !sd2) return fail(OCTSEG_BAD_ARG, "null argument");
+  if ((uintptr_t)scratch & 7) return fail(OCTSEG_BAD_ARG, "stack_signed_distance: scratch must be 8-byte aligned");
+  if (!extents_ok(N, H, W))
+    return fail(OCTSEG_BAD_SHAPE, "stack_signed_distance: empty batch or frame, or a side above 4096 (squared distances stay below 2^25)");
+  if (channels <= 0 || channels > MAX_CH) return fail(OCTSEG_BAD_SHAPE, "stack_signed_distance: not 1..16 channels");
+  if (scratch_bytes < signed_distance_scratch_bytes((size_t)N, H, W, channels))
+    return fail(OCTSEG_BAD_ARG, "stack_signed_distance: scratch is smaller than octseg_signed_distance_scratch_bytes(N, H, W, channels)");
+  if ((const void*)sd2 == (const void*)stack) return fail(OCTSEG_BAD_ARG, "stack_signed_distance: the output must not alias the input");
+  HIPCHK(launch_stack_signed_distance(stack, N, H, W, channels, scratch, sd2, (hipStream_t)stream));
+  return OCTSEG_OK;
+}
+
+int octseg_signed_blend(const int* sd2, int K, int H, int W, int channels, const int* plan, int M, float* out, int N_out, int* made, void* stream) {
+  if (!sd2 || !plan || !out) return fail(OCTSEG_BAD_ARG, "null argument");
+  if (!extents_ok(K, H, W) || N_out <= 0)
+    return fail(OCTSEG_BAD_SHAPE, "signed_blend: no key slice, no output slice or an empty frame, or a side above 4096");
+  if (channels <= 0 || channels > MAX_CH) return fail(OCTSEG_BAD_SHAPE, "signed_blend: not 1..16 channels");
+  if (M <= 0) return fail(OCTSEG_BAD_SHAPE, "signed_blend: a plan of no rows");
+  if ((const void*)out == (const void*)sd2) return fail(OCTSEG_BAD_ARG, "signed_blend: the output must not alias the maps");
+  HIPCHK(launch_signed_blend(sd2, K, H, W, channels, plan, M, out, N_out, made, (hipStream_t)stream));
   return OCTSEG_OK;
 }
 

@@ -449,6 +449,12 @@ hipError_t launch_volume_pair_counts(const float* src, const float* dst, int N, 
 hipError_t launch_volume_pair_query(const float* src, const float* dst, int N, int H, int W, int Ca, int Cb, const int* pairs, int P, int src_part,
                                     int dst_part, int slice_step, int rows, void* scratch, long long seg0, const long long* offsets, long long* keys,
                                     long long capacity, int* overflow, unsigned long long* minout, hipStream_t st);
+// signed squared distance maps and the blend of two of them by integer weights (distance.hip): sd2 int32 [N][C][H][W], + inside,
+// - outside, never 0; plan device int32 [M][6] = (channel, out_slice, lo, hi, w_lo, w_hi), out f32 [Nout][H][W][C], made (may be null) int32 [M].
+// scratch: signed_distance_scratch_bytes(N, H, W, C) device bytes
+size_t signed_distance_scratch_bytes(size_t N, int H, int W, int C);
+hipError_t launch_stack_signed_distance(const float* stack, int N, int H, int W, int C, void* scratch, int* sd2, hipStream_t st);
+hipError_t launch_signed_blend(const int* sd2, int K, int H, int W, int C, const int* plan, int M, float* out, int Nout, int* made, hipStream_t st);
 
 // centrelines (skeleton.hip): Guo and Hall's thinning of every plane by one workgroup per plane, all passes in one launch -- from
 // the padded LDS image of planepass.h when skeleton_fits_lds(H, W) and force_global == 0, else over ping-pong images in scratch --, and the census

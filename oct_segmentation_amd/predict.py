@@ -309,6 +309,21 @@ def _main_volume(cfg, device, dtypes, log):
         _save_contours(res.stack, names, save_dir)
 
 
+def _bridge(stack, paths, names, max_gap, save_dir):
+    """``bridge=K``: the stack with gaps of at most K slices filled (``interp.bridge_gaps`` over the slices in sorted file-name order), in the
+    order it came in, and ``{save_dir}/bridge.json``, ``interp.bridge_report`` of what was made."""
+    from .interp import bridge_gaps, bridge_report
+    order = sorted(range(len(paths)), key=lambda i: os.path.basename(paths[i]))
+    index = torch.tensor(order, device=stack.device)
+    bridged, plan, made = bridge_gaps(stack[index], max_gap=max_gap, return_plan=True)
+    with open(os.path.join(save_dir, 'bridge.json'), 'w') as f:
+        json.dump({'max_gap': int(max_gap), 'images': [names[i] for i in order],
+                   'classes': bridge_report(plan, made, [names[i] for i in order], channels=int(stack.shape[3]))}, f)
+    out = torch.empty_like(bridged)
+    out[index] = bridged
+    return out
+
+
 def _save_lumen(report, save_dir):
     """``lumen=true``: ``{save_dir}/lumen.json``, ``shape.lumen_report`` of the stack that is rendered and measured (after ``clean``)."""
     with open(os.path.join(save_dir, 'lumen.json'), 'w') as f:
@@ -399,6 +414,10 @@ def main(argv=None):
     (``analysis.analyze_stack``), with the frames as the slices of one pullback in sorted file-name order, as the app sorts its mask files;
     ``clean`` (default false): the mask stack goes through ``cleanup.clean_stack`` (the reference's ``MaskProcessor``: smoothing, the three
     largest components, hole fill) before it is rendered and measured;
+    ``bridge`` (default 0: off, nothing changes): after ``clean`` and before everything that is rendered or measured, gaps of at most ``bridge``
+    slices inside a class are filled by interpolation between the neighbouring slices (``interp.bridge_gaps``, slices in the order ``analysis``
+    uses) and ``{save_dir}/bridge.json`` (``interp.bridge_report``: per class the slices made, from which, how many pixels) is written; image
+    files only;
     ``plaque`` (default false): also write ``{save_dir}/plaque.json``, the polar plaque report of the same stack (``polar.plaque_report``: lipid
     arc, cap thickness where lipid lies behind it), and ``plaque_carpet.png`` (``polar.carpet_view``), slices in the order ``analysis`` uses;
     ``lesions`` (default false): also write ``{save_dir}/lesions.json``, the 3-D lesion report of the same stack (``lesions.lesion_report``:
@@ -442,7 +461,12 @@ def main(argv=None):
     if not paths:
         raise FileNotFoundError(f'no images under {cfg["data_dir"]}')
     os.makedirs(str(cfg['save_dir']), exist_ok=True)
+    bridge = int(cfg.get('bridge') or 0)
+    if bridge < 0:
+        raise ValueError(f'bridge must be an integer >= 0 (the longest gap of slices to fill; 0 is off), got {bridge}')
     if str(cfg['data_dir']).endswith('.npy'):
+        if bridge:                      # analyze_pullback renders and measures inside: refuse, do not quietly serve the unbridged stack
+            raise ValueError('bridge applies to image files only: a .npy volume goes through pullback.analyze_pullback, which does not bridge')
         if thresholds is not None:      # analyze_pullback segments at 0.5: refuse, do not quietly serve the default cut
             raise ValueError('thresholds apply to image files only: a .npy volume goes through pullback.analyze_pullback, which cuts at 0.5')
         _main_volume(cfg, device, dtypes, log)
@@ -475,6 +499,8 @@ def main(argv=None):
     if bool(cfg.get('clean', False)):
         from .cleanup import clean_stack
         stack = clean_stack(stack)
+    if bridge:
+        stack = _bridge(stack, paths, names, bridge, str(cfg['save_dir']))
     torch.cuda.synchronize()
     log.info(f'Prediction time: {time.time() - start_inference:.1f} s')
     save_results(images, stack, names, cfg['classes'], str(cfg['save_dir']), close_iterations=int(cfg.get('close_iterations', 1)))
